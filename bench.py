@@ -8,10 +8,15 @@ int8 LLRs already resident in HBM. One step = one decode of the whole per-GPU ba
 Multi-GPU (torchrun, one process per GPU, RCCL): every rank generates and decodes its own
 shard of frames (weak scaling, no data-path collective); timing is max over ranks.
 
-Prints ONE JSON line (rank 0). Extra fields:
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps decodes and prints
+the headline (value, ms_per_step) with the roofline of the timed kernel:
   roofline     -- HBM roofline of the decode kernel: algorithmic bytes per launch
                   (1.125 N bytes per frame: N int8 LLRs in + N/8 bytes of x^ out) / mean
                   kernel duration (HIP events on the launch stream)
+--dump-outputs DIR writes what the last timed step decoded (DIR/xhat.npy, see dump_outputs).
+--full adds every measurement and check that takes runs of its own: the oracle parity check and
+the error rates of the last decoded batch, the Eb/N0 sweep, the two-stream loop, the secondary
+configurations and
   cpu_baseline -- the CPU oracle (literal C restatement of my_module::do_action, one thread)
                   timed on a bounded sample on this host, rank 0 / N=1 only
 """
@@ -404,6 +409,25 @@ def secondary_entry(torch, pkg, sharding, dist, coll_dev, args, key, mask_name, 
     return ent
 
 
+DUMP_BYTES = 32 << 20   # --dump-outputs: float32 bits of at most this many bytes per rank
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(torch, pkg, out, N, path):
+    """--dump-outputs: x^ of the last timed step as a caller of Decoder.decode() receives it
+    (`out`: int64 [B, ceil(N/64)], bit i of word j = x^[64j+i]), unpacked to float32 0 / 1
+    [frames, N]. A batch larger than DUMP_BYTES is sampled: a fixed seeded choice of frames
+    (sorted), the same for every run of the same batch size."""
+    B = out.shape[0]
+    keep = max(1, min(B, DUMP_BYTES // (4 * N)))
+    rows = np.arange(B)
+    if keep < B:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, keep, replace=False))
+    words = out[torch.from_numpy(rows).to(out.device)].cpu().numpy()
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.save(path, pkg.unpack_bits(words, N).astype(np.float32))
+
+
 def time_scatter_gather(torch, pkg, sharding, dist, dec, mask, total, rank, dev, cdev, args):
     """C4 flow: rank 0 holds `total` frames in HBM; per step RCCL scatters the LLR shards,
     every rank decodes its shard, RCCL gathers x^ to rank 0. Returns timing (max over ranks)."""
@@ -451,6 +475,14 @@ def main():
                          "N in {8, 512, 1024}, else all-zero; xorshift128 seed 0xF0; Box-Muller; beta 4, +-31), "
                          "each rank taking the next frames of the global stream; torch: random information "
                          "bits + torch AWGN")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the oracle parity check and the error "
+                         "rates of the last decoded batch, the Eb/N0 sweep, the two-stream loop, the secondary "
+                         "configurations and the CPU baseline (each can be switched off below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x^ of the last timed step to DIR/xhat.npy (float32 0 / 1 [frames, N]; a fixed "
+                         "seeded sample of the frames when the batch is larger than %d MB; xhat_rank<r>.npy "
+                         "for every rank of a multi-GPU run)" % (DUMP_BYTES >> 20))
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--host-io", action="store_true",
@@ -528,8 +560,14 @@ def main():
 
     elapsed, kern_ms = timed_decodes(torch, sharding, dist, coll_dev, dec, batches, outs, args.steps, args.warmup,
                                      stream, settle_s=args.settle_ms * 1e-3)
+    # the last launch of the timed loop decoded batch (steps - 1) % nb into its output
+    last = (args.steps - 1) % nb
+    if args.dump_outputs:   # (before anything else decodes into the output buffers)
+        dump_outputs(torch, pkg, outs[last], N,
+                     os.path.join(args.dump_outputs, "xhat.npy" if world == 1 else "xhat_rank%d.npy" % rank))
     # the CPU baseline decodes the head of the first resident batch (the GPU run's own LLRs)
-    cpu_llr = batches[0][0][: max(8, min(4096, int(2 ** 22 // N)))].cpu().numpy() if rank == 0 else None
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_llr = batches[0][0][: max(8, min(4096, int(2 ** 22 // N)))].cpu().numpy() if want_cpu else None
     if dist is not None:   # frames decoded by all ranks (shards may differ by a few frames)
         cnt = torch.tensor([per_gpu], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(cnt)
@@ -540,8 +578,6 @@ def main():
     total_frames = frames_all * args.steps
     fps = total_frames / elapsed
     value = fps * K
-    # the last launch of the timed loop decoded batch (steps - 1) % nb into its output
-    last = (args.steps - 1) % nb
     llr, xref, x = batches[last]
     out = outs[last]
 
@@ -553,16 +589,16 @@ def main():
     # parity spot check (rank 0) vs the CPU oracle on the first frames of the batch; after the
     # timed region, so the oracle's CPU threads cannot perturb it
     check = {}
-    if rank == 0 and args.check > 0:
+    if args.full and rank == 0 and args.check > 0:
         from oracle import oracle
         nchk = min(args.check, per_gpu)
         got = pkg.unpack_bits(out[:nchk].cpu().numpy(), N)
         ref = oracle.decode_fsm(mask, llr[:nchk].cpu().numpy())
         check = {"frames": nchk, "bit_exact": bool((got == ref).all())}
 
-    # error rates of the last decoded batch vs the transmitted codewords (informative)
-    errors_all = None
-    if xref is not None:
+    # error rates of the last decoded batch vs the transmitted codewords (informative; --full)
+    errors_all, fer, ber = None, None, None
+    if args.full and xref is not None:
         # sc_error_counter semantics on the device (per-frame count mod 1024), whole batch
         cnt = pkg.count_errors(out, xref, N)
         torch.cuda.synchronize()
@@ -581,7 +617,7 @@ def main():
                           "bit_error_rate": t[2] / (frames_all * N),
                           "per_rank": [{"frames": counts[r], "frame_errors": int(v[1].item()),
                                         "bit_errors": int(v[2].item())} for r, v in enumerate(per_rank)]}
-    else:
+    elif args.full:
         xhat = pkg.unpack_bits(out[: min(per_gpu, 4096)].cpu().numpy(), N)
         xs = x[: xhat.shape[0]].cpu().numpy()
         fer = float((xhat != xs).any(axis=1).mean())
@@ -590,7 +626,7 @@ def main():
     # (after the parity check and the error counts: the sweep reuses the output buffers)
     # Eb/N0 sweep: the same timed loop on frames at each SNR
     sweep = None
-    if args.ebn0_sweep:
+    if args.full and args.ebn0_sweep:
         sweep = []
         for e in EBN0_SWEEP:
             bs = make_batches(pkg, torch, args, mask, per_gpu, frame0, sum(counts), dev, e, nb)
@@ -608,7 +644,7 @@ def main():
 
     # two batches in flight (after the sweep, before the secondary plans allocate)
     pipelined = None
-    if dec.stats["storage"] != 1:
+    if args.full and dec.stats["storage"] != 1:
         el2 = pipelined_decodes(torch, sharding, dist, coll_dev, dec, batches, args.steps, dev)
         pipelined = {"streams": 2, "ms_per_step": el2 / args.steps * 1e3,
                      "value": frames_all * args.steps / el2 * K, "vs_one_stream": elapsed / el2,
@@ -616,7 +652,7 @@ def main():
                              "tail overlaps the next one's start; value above is the one-stream loop"}
 
     secondary = None
-    if args.secondary and args.config == "c2" and not args.batch:
+    if args.full and args.secondary and args.config == "c2" and not args.batch:
         secondary = {}
         for key, mname, pg, fmt, note in SECONDARY:
             if key in ("c5_share64", "c4_share") and world != 1:
@@ -695,7 +731,7 @@ def main():
                               "note": "polar_sc_decode_host: %d frames from pageable host memory "
                                       "(%.1f MB in, %.1f MB out), copies + decode, synchronous"
                                       % (per_gpu, per_gpu * N / 1e6, per_gpu * dec.words * 8 / 1e6)}
-        if world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             res["cpu_baseline"] = cpu_baseline(mask, args.cpu_seconds, args.ebn0, cpu_llr)
         print(json.dumps(res))
     if dist is not None:

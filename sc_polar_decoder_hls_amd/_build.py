@@ -136,19 +136,18 @@ def _run_pool(items, procs, verbose):
         for r in res:
             _report(r, verbose)
         return
-    # (a pool whose workers cannot start -- e.g. the parent runs a script from stdin, which
-    # spawned children cannot re-import -- raises BrokenProcessPool instead of hanging: then
+    # (a pool whose workers cannot start raises BrokenProcessPool instead of hanging: then
     # compile in-process)
     from concurrent.futures import ProcessPoolExecutor, as_completed
     from concurrent.futures.process import BrokenProcessPool
-    # (python -c has no __main__ file and spawns fine; python - / a REPL names one that is
-    # not a file, which spawned children would try to import)
+    # Spawned children re-import the parent's __main__ by its spec name or its file: a script
+    # from stdin or a string names a file that does not exist (the children would die), and a
+    # script without a __main__ guard would run again in every child. The workers need this
+    # module only, so __main__ shows neither while they start.
     main = sys.modules.get("__main__")
-    mfile = getattr(main, "__file__", None)
-    if mfile is not None and not os.path.isfile(mfile):
-        for r in map(_compile_item, items):
-            _report(r, verbose)
-        return
+    hidden = {k: main.__dict__.pop(k) for k in ("__file__", "__spec__") if main is not None and k in main.__dict__}
+    if hidden:
+        main.__spec__ = None
     done = set()
     try:
         with ProcessPoolExecutor(procs, mp_context=mp.get_context("spawn")) as ex:
@@ -160,6 +159,10 @@ def _run_pool(items, procs, verbose):
         for i, it in enumerate(items):
             if i not in done:
                 _report(_compile_item(it), verbose)
+    finally:
+        if hidden:
+            del main.__spec__
+            main.__dict__.update(hidden)
 
 
 def _report(r, verbose):
@@ -170,26 +173,27 @@ def _report(r, verbose):
 
 
 def _default_procs():
-    # a C5 hybrid / pair compile holds a few GB: bounded by memory as well as cores
-    return int(os.environ.get("POLAR_SC_PREWARM_PROCS", min(6, os.cpu_count() or 1)))
-
-
-def prewarm_plans(plans, procs=None, verbose=False):
-    """Compile the hipRTC kernels of [(name, info mask, tuning dict)] into the code-object cache
-    (host only, in parallel worker processes, largest first)."""
-    _run_pool([(n, m, None, t) for n, m, t in plans], procs or _default_procs(), verbose)
+    """Worker processes of the prewarm: POLAR_SC_PREWARM_PROCS, else MAX_JOBS (the job limit of a
+    shared build host, whose os.cpu_count() may count CPUs this job does not own), else the CPUs
+    this process may run on, at most 16; and one per 3 GB of available memory (a C5 pair compile
+    holds a few GB, and the largest codes are compiled first, i.e. all at once)."""
+    for var in ("POLAR_SC_PREWARM_PROCS", "MAX_JOBS"):
+        if os.environ.get(var, "").isdigit() and int(os.environ[var]) > 0:
+            return int(os.environ[var])
+    try:
+        procs = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        procs = os.cpu_count() or 1
+    try:
+        with open("/proc/meminfo") as f:
+            avail_kb = next(int(line.split()[1]) for line in f if line.startswith("MemAvailable:"))
+        procs = min(procs, avail_kb // (3 << 20))
+    except (OSError, StopIteration, ValueError):
+        pass
+    return max(1, min(16, procs))
 
 
 def prewarm_items(items, procs=None, verbose=False):
     """Compile the hipRTC kernels of [(name, info mask, config fields dict or None, tuning dict
     or None)] into the code-object cache (host only, in parallel)."""
     _run_pool(list(items), procs or _default_procs(), verbose)
-
-
-def prewarm(masks, configs=(None,), procs=None, verbose=False):
-    """Compile the hipRTC kernels of the plans of `masks` ({name: info mask}) x `configs`
-    into the on-disk code-object cache next to the library (lib/rtc_cache/), host only, in
-    parallel. A GPU box then loads them instead of compiling (the C5 hybrid kernel takes about
-    two minutes of hipRTC)."""
-    items = [(n, m, _cfg_fields(c), None) for n, m in masks.items() for c in configs]
-    _run_pool(items, procs or _default_procs(), verbose)

@@ -349,33 +349,53 @@ def sweep_items():
     return out
 
 
-def prewarm_all(verbose=False):
-    """Compile every plan above (and the reference-config plan of every mask fixture) into
-    lib/rtc_cache/."""
-    import sc_polar_decoder_hls_amd as pkg
-    from sc_polar_decoder_hls_amd import _build
-    _build.prewarm({n: mask(n) for n in mask_names() if mask(n).size >= 32}, verbose=verbose)
+def all_items():
+    """(name, mask, config fields or None, tuning or None) of every plan above and of the
+    reference-config plan of every mask fixture."""
+    items = [(n, mask(n), None, None) for n in mask_names() if mask(n).size >= 32]
     # the schedule interpreter of every datapath format the GPU tests exercise (LDS and
     # HBM-scratch storage): its source depends on the format, not on the mask
-    cfgs = []
-    for par, sigmag, ext, q in FORMATS:
-        c = pkg.default_config()
-        c.par, c.sigmag, c.extended, c.llr_bits = par, sigmag, ext, q
-        cfgs.append(c)
-    _build.prewarm({n: mask(n) for n in ("FB_N1024_K512", "frozen_n_16384_k_8192")}, configs=cfgs, verbose=verbose)
-    q8 = pkg.default_config()
-    q8.llr_bits = 8
-    _build.prewarm({n: mask(n) for n in RATE09_MASKS}, configs=[q8], verbose=verbose)
-    _build.prewarm_plans(gpu_plans() + solo_plans() + cpu_test_plans(), verbose=verbose)
-    _build.prewarm_items(gpu_par64_plans(), verbose=verbose)
+    fmts = [{"par": par, "sigmag": sigmag, "extended": ext, "llr_bits": q} for par, sigmag, ext, q in FORMATS]
+    items += [(n, mask(n), c, None) for n in ("FB_N1024_K512", "frozen_n_16384_k_8192") for c in fmts]
+    items += [(n, mask(n), {"llr_bits": 8}, None) for n in RATE09_MASKS]
+    items += [(n, m, None, t) for n, m, t in gpu_plans() + solo_plans() + cpu_test_plans()]
+    items += gpu_par64_plans()
     # the pruning / ELAG / format sweeps: PRUNING_LEVEL 1 leaf decoders and EXTENDED 0 run the
     # generated kernels (one code object per mask and configuration); the interpreter formats
     # share one per format
-    _build.prewarm_items(sweep_items(), verbose=verbose)
-    _build.prewarm_items(ca2_items(), verbose=verbose)
-    _build.prewarm_items(q9_items(), verbose=verbose)
-    _build.prewarm_items(par48_gpu_items(), verbose=verbose)
-    _build.prewarm_items(high_rate_items(), verbose=verbose)
+    items += sweep_items() + ca2_items() + q9_items() + par48_gpu_items() + high_rate_items()
+    return items
+
+
+def prewarm_all(verbose=False):
+    """Compile every plan of all_items() into lib/rtc_cache/: each distinct plan once, all of
+    them in one pool of worker processes (a clean build compiles ~650 kernels, hours of one
+    CPU: no stage waits for the longest compile of the one before). Plans whose generated
+    source another plan already has go second, so that no two workers compile the same source
+    at the same time; they find it cached and compile at most their alternate layout."""
+    import hashlib
+    import sc_polar_decoder_hls_amd as pkg
+    from sc_polar_decoder_hls_amd import _build
+    default = _build._cfg_fields(pkg.default_config())
+    plans, sources, first, second = set(), set(), [], []
+    for item in all_items():
+        _, m, cfg, tun = item
+        cfg = dict(default, **(cfg or {}))
+        key = (m.tobytes(), tuple(sorted(cfg.items())), tuple(sorted((k, v) for k, v in (tun or {}).items() if v)))
+        if key in plans:
+            continue
+        plans.add(key)
+        c = pkg.default_config()
+        for k, v in cfg.items():
+            setattr(c, k, v)
+        dec = pkg.Decoder(m, c, tuning=tun)
+        src = dec.kernel_source()
+        dec.close()
+        h = hashlib.sha1(src.encode()).digest() if src is not None else None
+        (second if h in sources else first).append(item)
+        sources.add(h)
+    _build.prewarm_items(first, verbose=verbose)
+    _build.prewarm_items(second, verbose=verbose)
 
 
 # ---- high-rate codes across the formats (tests/test_gpu_formats.py

@@ -1105,8 +1105,11 @@ int polar_sc_plan_destroy(polar_sc_plan *p)
         if (kv.second.llr) (void)hipFree(kv.second.llr);
         if (kv.second.out) (void)hipFree(kv.second.out);
     }
+    // (a plan that never reached a device holds nothing there: no HIP call, which would open the
+    // GPU in a host-only process -- and a process with the GPU open compiles its next generated
+    // kernel with hipRTC instead of the clang driver, polar_sc_jit.cpp gpu_open)
     int cur = 0;
-    bool have_dev = hipGetDevice(&cur) == hipSuccess;
+    bool have_dev = !p->dev.empty() && hipGetDevice(&cur) == hipSuccess;
     for (auto &kv : p->dev) {
         if (have_dev) (void)hipSetDevice(kv.first);
         if (kv.second.ops) (void)hipFree(kv.second.ops);

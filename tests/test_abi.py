@@ -158,11 +158,16 @@ def test_loader_errors(pkg, tmp_path):
         pkg.load_mask_file(str(bad))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Frozen_Bit_Tab"), reason="reference tree absent")
-def test_loaders_on_reference_tables(pkg):
+def test_loaders_on_reference_tables(pkg, tmp_path):
+    """every reference table file (tests/golden/ref_tables.npz holds their bytes,
+    tools/make_golden.py) through the loaders"""
     masks = util.masks()
+    tables = np.load(os.path.join(util.ROOT, "tests", "golden", "ref_tables.npz"), allow_pickle=False)
+    assert set(tables.files) == set(masks)
     for name, m in masks.items():
-        path = os.path.join("/root/reference", m["source"])
+        path = str(tmp_path / os.path.basename(m["source"]))
+        with open(path, "wb") as f:
+            f.write(tables[name].tobytes())
         got = pkg.load_frozen_tab(path, K=m["K"], N=m["N"]) if m["format"] == "tab" else pkg.load_mask_file(path)
         np.testing.assert_array_equal(got, util.mask(name), err_msg=name)
 

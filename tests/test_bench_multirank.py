@@ -27,7 +27,7 @@ def test_bench_two_ranks_gloo(pkg, cuda):
     env = dict(os.environ, POLAR_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--io", "scatter",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--io", "scatter",
            "--no-ebn0-sweep", "--settle-ms", "0", "--check", "8"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert res.returncode == 0, res.stderr[-4000:]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU measurement at HEAD (one script for every round; run from gpurun):
 #   tests   -- the whole -m gpu suite and smoke()
-#   bench   -- the default bench line (C2 headline + secondary entries + CPU baseline) and a
+#   bench   -- the full bench line (C2 headline + secondary entries + CPU baseline) and a
 #              driver-shaped short run (--steps 20 --warmup 5)
 #   prof    -- per config: kernel-trace stats, FETCH_SIZE and WRITE_SIZE (separate passes, the
 #              gfx950 PMC slot limits), two SQ passes; tools/prof_decode.py records the launch
@@ -38,9 +38,9 @@ for step in "$@"; do
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
     echo "smoke ok" ;;
   bench)
-    timeout -k 10 500 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout -k 10 500 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
     echo "bench ok"
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"
+    timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"
     echo "bench steps20 ok" ;;
   prof)
     for c in "c2 FB_N1024_K512 65536 10" "c4share FB_N1024_K512 131072 10" "c3 frozen_n_65536_k_32768 4096 4" "c5 frozen_n_262144_k_131072 512 3" \

@@ -9,7 +9,8 @@ known-answer data it holds are:
     Generated_Frozen_Bit/frozen_n_*_k_*.txt 0/1 masks) -> data/frozen_masks.json,
     stored as derived information-bit masks (bit i of the mask = frozen-table bit i,
     1 = information, packed LSB-first and hex-encoded), with the rule that derived them
-    (Frozen_Bit_Generator/src/Writer.h:35-105).
+    (Frozen_Bit_Generator/src/Writer.h:35-105); and the table files themselves, byte for
+    byte -> tests/golden/ref_tables.npz (tests/test_abi.py reads them through the loaders).
 
 Nothing here is executed at test/bench time; /root/reference does not exist on the GPU box.
 """
@@ -17,6 +18,8 @@ import json
 import os
 import re
 import sys
+
+import numpy as np
 
 REF = os.environ.get("POLAR_REF", "/root/reference")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -90,6 +93,15 @@ TABLES = [
 ]
 
 
+def write_tables():
+    """tests/golden/ref_tables.npz: {table name: the bytes of its reference file (uint8)}"""
+    files = {}
+    for name, _, rel, _, _ in TABLES:
+        with open(os.path.join(REF, rel), "rb") as f:
+            files[name] = np.frombuffer(f.read(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(ROOT, "tests/golden/ref_tables.npz"), **files)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("reference tree not found at %s" % REF)
@@ -118,7 +130,8 @@ def main():
                     "frozen-table bit i, 1 = information bit",
             "masks": masks,
         }, f, indent=1)
-    print("wrote kat_codewords.json and frozen_masks.json (%d masks)" % len(masks))
+    write_tables()
+    print("wrote kat_codewords.json, frozen_masks.json and ref_tables.npz (%d masks)" % len(masks))
 
 
 if __name__ == "__main__":
