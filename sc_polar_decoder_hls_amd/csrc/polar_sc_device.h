@@ -515,13 +515,23 @@ __device__ __forceinline__ u32 G_root(u32 a, u32 b, u32 u, u32 &S)
 }
 // G on split words: X = plane of sign(a') ^ sign(b); returns the clamped magnitude and puts
 // |a| < |b| into LT. The output sign plane is then sign(b) ^ (X & ~LT) per 16 words.
+// One multiply-add gives both cases: the mask OR 1 is -1 / +1 per half, so t = ma - mb where the
+// signs differ and ma + mb (>= 0, below 2^15) where they agree; |t| is the magnitude either
+// way. LT takes t's sign bit: |a| < |b| where X is set and 0 where it is clear, which is all
+// X & ~LT reads of it. (-DPOLAR_G_BSEL: subtract, add and a bitwise select, for A/Bs)
 template <int I>
 __device__ __forceinline__ u32 G_split(u32 ma, u32 mb, u32 X, u32 &LT)
 {
     const u32 xm = opaque(plane_mask<I>(X));
+#ifndef POLAR_G_BSEL
+    const u32 t = pk_mad_u16(mb, xm | 0x00010001u, ma);
+    LT = plane_put<I>(LT, t);
+    return pk_min(pk_abs_i16(t), GSAT2);
+#else
     const u32 d = pk_sub(ma, mb);
     LT = plane_put<I>(LT, d);
     return pk_min(bsel(xm, pk_abs_i16(d), pk_add(ma, mb)), GSAT2);
+#endif
 }
 // REP word from split parent words: F value + 512 per half, and its SM16 form
 template <int I>

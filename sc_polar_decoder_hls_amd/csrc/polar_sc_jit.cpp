@@ -213,7 +213,7 @@ struct Gen {
     // LDS-bound.) Every channel word becomes a magnitude pair m<LG>[w] and a bit of the sign
     // plane s<LG>[w / 16] (two LDS tables give |LLR| and the sign of a channel byte), so the
     // root F / G are the split-word ops of every other level (F: 1 VALU per word instead of
-    // 10, G: 10 instead of 18) for a conversion of about 3 VALU per word.
+    // 10, G: 9 instead of 18) for a conversion of about 3 VALU per word.
     void root_presplit(int words)
     {
         for (int k = 0; k < planes(words); k++) o << "  s" << LG << "[" << k << "] = 0u;\n";
@@ -223,6 +223,15 @@ struct Gen {
             // j hi) give its magnitudes by one mask and the sign-plane bits of words i and j by
             // one shift + and-or each (bits 7 / 23 and 15 / 31 land on bits i % 16 / 16 + i % 16)
             const int h = words / 2;
+            // Whole planes per half (h a multiple of 16): the four sign bits of a register are
+            // collected instead of placed. Over 8 consecutive registers
+            // acc = (acc >> 1) | (r_ & 0x80808080) leaves in byte 0 / 1 / 2 / 3 of acc the signs
+            // of words i0..i0+7 low frame / j0..j0+7 low / i0.. high / j0.. high, in plane bit
+            // order; one v_perm_b32 of two accumulators (16 words) is a plane. 2 VALU per
+            // register and 2 per 16 instead of 4 per register. (-DPOLAR_PRESPLIT_SIGN_PUT: the
+            // former placing, for A/Bs)
+            const bool collect = h % 16 == 0;
+            if (collect) o << "#ifndef POLAR_PRESPLIT_TABS\n#ifndef POLAR_PRESPLIT_SIGN_PUT\n  u32 sa_[2];\n#endif\n#endif\n";
             for (int i = 0; i < h; i++) {
                 const int j = i + h, si = 7 - i % 16, sj = 15 - j % 16;
                 const std::string shi = si >= 0 ? "(r_ >> " + std::to_string(si) + ")" : "(r_ << " + std::to_string(-si) + ")";
@@ -237,9 +246,20 @@ struct Gen {
                   << "  { const u32 r_ = (u32)tab8_[chl[" << 16 * i << "]] | ((u32)tab8_[chl[" << 16 * j << "]] << 8) | ((u32)tab8_[chh["
                   << 16 * i << "]] << 16) | ((u32)tab8_[chh[" << 16 * j << "]] << 24);\n"
                   << "#endif\n"
-                  << "    pr[" << i << "] = r_ & (QMAG * 0x01010101u);\n"
-                  << "    s" << LG << "[" << i / 16 << "] |= " << shi << " & " << (0x00010001u << (i % 16)) << "u;\n"
-                  << "    s" << LG << "[" << j / 16 << "] |= (r_ >> " << sj << ") & " << (0x00010001u << (j % 16)) << "u; }\n"
+                  << "    pr[" << i << "] = r_ & (QMAG * 0x01010101u);\n";
+                if (collect) {
+                    const int a = (i / 8) % 2;
+                    o << "#ifndef POLAR_PRESPLIT_SIGN_PUT\n    sa_[" << a << "] = ";
+                    if (i % 8) o << "(sa_[" << a << "] >> 1) | ";
+                    o << "(r_ & 0x80808080u);\n";
+                    if (i % 16 == 15)
+                        o << "    s" << LG << "[" << i / 16 << "] = __builtin_amdgcn_perm(sa_[1], sa_[0], 0x06020400u);\n"
+                          << "    s" << LG << "[" << j / 16 << "] = __builtin_amdgcn_perm(sa_[1], sa_[0], 0x07030501u);\n";
+                    o << "#else\n";
+                }
+                o << "    s" << LG << "[" << i / 16 << "] |= " << shi << " & " << (0x00010001u << (i % 16)) << "u;\n"
+                  << "    s" << LG << "[" << j / 16 << "] |= (r_ >> " << sj << ") & " << (0x00010001u << (j % 16)) << "u;\n"
+                  << (collect ? "#endif\n" : "") << "  }\n"
                   // (A/B: -DPOLAR_PRESPLIT_TABS, the separate magnitude and sign tables of round 2)
                   << "#else\n"
                   << "  { const u32 a0_ = chl[" << 16 * i << "], a1_ = chh[" << 16 * i << "], b0_ = chl[" << 16 * j
