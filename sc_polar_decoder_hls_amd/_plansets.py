@@ -363,8 +363,21 @@ def all_items():
     # the pruning / ELAG / format sweeps: PRUNING_LEVEL 1 leaf decoders and EXTENDED 0 run the
     # generated kernels (one code object per mask and configuration); the interpreter formats
     # share one per format
-    items += sweep_items() + ca2_items() + q9_items() + par48_gpu_items() + high_rate_items()
+    items += sweep_items() + ca2_items() + q9_items() + par48_gpu_items() + high_rate_items() + issue_form_items()
     return items
+
+
+# ---- the multi-plane SPC flip of the generated register decoders (tests/test_issue_forms_gpu.py):
+# an SPC node of 128 words inside a hybrid plan's subtrees of 128 words -------------------------
+def wide_spc_mask():
+    m = mask("frozen_n_4096_k_2048").copy()
+    m[1024:2048] = 1
+    m[1024] = 0
+    return m
+
+
+def issue_form_items():
+    return [("wide_spc4096", wide_spc_mask(), None, {"kernel": 2, "sub_words": 128})]
 
 
 def prewarm_all(verbose=False):

@@ -138,7 +138,23 @@ __device__ __forceinline__ u32 G_sm(u32 a, u32 b, u32 u)
 #endif
 __device__ __forceinline__ u32 lane_pos(u32 lane)
 {
+#ifndef POLAR_LANE_SELECT
+    return POLAR_LANE_REMAP ? (lane ^ (((lane >> 2) & 1u) * 3u)) : lane;
+#else
     return POLAR_LANE_REMAP ? (lane ^ ((lane & 4u) ? 3u : 0u)) : lane;
+#endif
+}
+// all-ones where bit B of v is clear, as arithmetic: written as a select the compiler may pick
+// v_cmp + v_cndmask_b32 on VCC for it and for every bsel that reads it.
+// (-DPOLAR_LANE_SELECT: the selects, for A/Bs)
+template <int B>
+__device__ __forceinline__ u32 clear_mask(u32 v)
+{
+#ifndef POLAR_LANE_SELECT
+    return ((v >> B) & 1u) - 1u;
+#else
+    return (v & (1u << B)) ? 0u : 0xFFFFFFFFu;
+#endif
 }
 
 // value of physical lane (l ^ H)
@@ -186,10 +202,10 @@ struct Lanes {
         pl = p;
         pos = lane_pos(p);
         br = ((pos & 1u) << 3) | ((pos & 2u) << 1) | ((pos & 4u) >> 1) | ((pos & 8u) >> 3);
-        a1 = (pos & 1u) ? 0u : 0xFFFFFFFFu;
-        a2 = (pos & 2u) ? 0u : 0xFFFFFFFFu;
-        a4 = (pos & 4u) ? 0u : 0xFFFFFFFFu;
-        a8 = (pos & 8u) ? 0u : 0xFFFFFFFFu;
+        a1 = clear_mask<0>(pos);
+        a2 = clear_mask<1>(pos);
+        a4 = clear_mask<2>(pos);
+        a8 = clear_mask<3>(pos);
     }
 };
 
@@ -283,10 +299,10 @@ __device__ __forceinline__ u32 row_xor(u32 v)
 __device__ __forceinline__ u32 row_transpose16(u32 v, const Lanes &ln)
 {
     u32 p;
-    p = xorlane_phys<8>(v); v = bsel((((ln.pl & 8u) != 0u) ? 0u : 0xFFFFFFFFu), (v & 0x00FF00FFu) | ((p & 0x00FF00FFu) << 8), ((p >> 8) & 0x00FF00FFu) | (v & 0xFF00FF00u));
-    p = xorlane_phys<4>(v); v = bsel((((ln.pl & 4u) != 0u) ? 0u : 0xFFFFFFFFu), (v & 0x0F0F0F0Fu) | ((p & 0x0F0F0F0Fu) << 4), ((p >> 4) & 0x0F0F0F0Fu) | (v & 0xF0F0F0F0u));
-    p = xorlane_phys<2>(v); v = bsel((((ln.pl & 2u) != 0u) ? 0u : 0xFFFFFFFFu), (v & 0x33333333u) | ((p & 0x33333333u) << 2), ((p >> 2) & 0x33333333u) | (v & 0xCCCCCCCCu));
-    p = xorlane_phys<1>(v); v = bsel((((ln.pl & 1u) != 0u) ? 0u : 0xFFFFFFFFu), (v & 0x55555555u) | ((p & 0x55555555u) << 1), ((p >> 1) & 0x55555555u) | (v & 0xAAAAAAAAu));
+    p = xorlane_phys<8>(v); v = bselo(clear_mask<3>(ln.pl), (v & 0x00FF00FFu) | ((p & 0x00FF00FFu) << 8), ((p >> 8) & 0x00FF00FFu) | (v & 0xFF00FF00u));
+    p = xorlane_phys<4>(v); v = bselo(clear_mask<2>(ln.pl), (v & 0x0F0F0F0Fu) | ((p & 0x0F0F0F0Fu) << 4), ((p >> 4) & 0x0F0F0F0Fu) | (v & 0xF0F0F0F0u));
+    p = xorlane_phys<2>(v); v = bselo(clear_mask<1>(ln.pl), (v & 0x33333333u) | ((p & 0x33333333u) << 2), ((p >> 2) & 0x33333333u) | (v & 0xCCCCCCCCu));
+    p = xorlane_phys<1>(v); v = bselo(clear_mask<0>(ln.pl), (v & 0x55555555u) | ((p & 0x55555555u) << 1), ((p >> 1) & 0x55555555u) | (v & 0xAAAAAAAAu));
     return v;
 }
 
@@ -338,8 +354,16 @@ __device__ __forceinline__ u32 leaf_spc(u32 L, const Lanes &ln)
         klo = __builtin_elementwise_min(klo, xorlane<1>(klo));
         khi = __builtin_elementwise_min(khi, xorlane<1>(khi));
     }
+    // the lane that holds the minimum flips: (min ^ own key) - 1 is negative only there (keys
+    // are 19 bits), and that bit 31, moved onto the half's sign bit, masks the parity. No
+    // compare and select. (-DPOLAR_LEAF_SPC_SELECT: the former form, for A/Bs)
+#ifndef POLAR_LEAF_SPC_SELECT
+    const u32 flo = (((klo ^ mlo0) - 1u) >> 16) & par & 0x8000u;
+    const u32 fhi = ((khi ^ mhi0) - 1u) & par & 0x80000000u;
+#else
     const u32 flo = (klo == mlo0) ? (par & 0x8000u) : 0u;
     const u32 fhi = (khi == mhi0) ? (par & 0x80000000u) : 0u;
+#endif
     return h ^ flo ^ fhi;
 }
 
@@ -366,7 +390,11 @@ __device__ __forceinline__ u32 sm8_of_byte(u32 b)
     constexpr u32 QP = 1u << QB;
     const u32 t = b & (QP - 1u);
     const u32 m = (t < QP - t ? t : QP - t) & QMAG;
-    return (t >= QP / 2u + 1u ? 0x80u : 0u) | m;
+#ifndef POLAR_SM8_SELECT
+    return (((QP / 2u - t) >> 24) & 0x80u) | m;   // t > QP / 2: the difference wraps negative
+#else
+    return (t >= QP / 2u + 1u ? 0x80u : 0u) | m;   // (the former select, for A/Bs)
+#endif
 }
 // Byte transpose inside a quad of lanes (the four lanes of positions 4q .. 4q + 3 of a word,
 // which lane_pos keeps together): lane k of the quad holds the dword of those positions of
@@ -490,6 +518,21 @@ __device__ __forceinline__ u32 plane_mask(u32 p)
 {
     return pk_sra(pk_shl(p, (unsigned short)(15 - I)), 15);
 }
+// bit I of each half of plane p -> the multiplier -1 / +1 per half (0xFFFF / 0x0001) of the
+// multiply-add G and REP words: 1 - 2 * bit, as bit * 0xFFFE + 1 per half in one 24-bit
+// multiply-add of the two isolated bits (the low half's 0xFFFE + 1 does not carry). A shift and
+// an AND that dual-issue plus one single-issue op, where the mask form takes two packed shifts
+// and an OR; bit 0 needs no shift. (-DPOLAR_PM1_MASK: plane_mask | 1, for A/Bs)
+template <int I>
+__device__ __forceinline__ u32 plane_pm1(u32 p)
+{
+#ifndef POLAR_PM1_MASK
+    const u32 b = (I == 0 ? p : p >> I) & 0x00010001u;
+    return b * 0xFFFEu + 0x00010001u;   // (17 x 16 bits: v_mad_u32_u24)
+#else
+    return plane_mask<I>(p) | 0x00010001u;
+#endif
+}
 // bits 15 / 31 of v -> bits I / 16 + I of the plane
 template <int I>
 __device__ __forceinline__ u32 plane_put(u32 acc, u32 v)
@@ -522,12 +565,12 @@ __device__ __forceinline__ u32 G_root(u32 a, u32 b, u32 u, u32 &S)
 template <int I>
 __device__ __forceinline__ u32 G_split(u32 ma, u32 mb, u32 X, u32 &LT)
 {
-    const u32 xm = opaque(plane_mask<I>(X));
 #ifndef POLAR_G_BSEL
-    const u32 t = pk_mad_u16(mb, xm | 0x00010001u, ma);
+    const u32 t = pk_mad_u16(mb, opaque(plane_pm1<I>(X)), ma);
     LT = plane_put<I>(LT, t);
     return pk_min(pk_abs_i16(t), GSAT2);
 #else
+    const u32 xm = opaque(plane_mask<I>(X));
     const u32 d = pk_sub(ma, mb);
     LT = plane_put<I>(LT, d);
     return pk_min(bsel(xm, pk_abs_i16(d), pk_add(ma, mb)), GSAT2);

@@ -367,7 +367,7 @@ struct Gen {
         case POLAR_OP_REP: {
             // value chain in two's complement; the exact SM chain only when a total is 0
             o << "#ifndef REP_FSB\n#ifndef POLAR_REP_FSB\n"
-                 "#define REP_FSB(I, a, b, fs) pk_mad_u16(pk_min(a, b), plane_mask<I>(fs) | 0x00010001u, 0x02000200u)\n"
+                 "#define REP_FSB(I, a, b, fs) pk_mad_u16(pk_min(a, b), plane_pm1<I>(fs), 0x02000200u)\n"
                  "#else\n#define REP_FSB(I, a, b, fs) F_split_biased<I>(a, b, fs)\n#endif\n#endif\n";
             o << "  { // REP n " << n << " pos " << op.pos << "\n    u32 acc_ = 0u, full_, FS_[" << np << "];\n";
             for (int k = 0; k < np; k++)
@@ -447,7 +447,24 @@ struct Gen {
                 if (k16) o << "#ifndef POLAR_SPC_KEY32\n    const u32 ilo_ = (klo_ >> 4) & 63u, ihi_ = (khi_ >> 4) & 63u;\n#else\n";
                 o << "    const u32 ilo_ = (klo_ >> 4) & 0xFFFFFu, ihi_ = (khi_ >> 4) & 0xFFFFFu;\n";
                 if (k16) o << "#endif\n";
-                o <<
+                // The flip: the condition as 0 / 1 shifted to the word's bit. A select between two
+                // constants is the 3-operand v_cndmask_b32 (its VOP2 form needs a register operand),
+                // where "cond ? 1 << s : 0" became a v_cndmask_b32 on VCC. (Tried and not kept: the
+                // condition itself as mask arithmetic, ((key ^ br) & 15) - 1 ANDed with the parity,
+                // without any compare -- 0.27 us slower at C2, profiles/r08_ab/summary.txt.)
+                // (-DPOLAR_SPC_FLIP_SELECT: the former selects)
+                o << "#ifndef POLAR_SPC_FLIP_SELECT\n"
+                     "    const bool flo_ = (par_ & 0x8000u) && (klo_ & 15u) == ln.br;\n"
+                     "    const bool fhi_ = (par_ & 0x80000000u) && (khi_ & 15u) == ln.br;\n";
+                if (n <= 16) {
+                    o << "    bw[" << op.pos / 16 << "] ^= ((u32)flo_ << (" << op.pos % 16 << " + ilo_)) | ((u32)fhi_ << ("
+                      << 16 + op.pos % 16 << " + ihi_));\n";
+                } else {
+                    for (int k = 0; k < n / 16; k++)
+                        o << "    bw[" << op.pos / 16 + k << "] ^= ((u32)(flo_ && (ilo_ >> 4) == " << k
+                          << "u) << (ilo_ & 15u)) | ((u32)(fhi_ && (ihi_ >> 4) == " << k << "u) << (16u + (ihi_ & 15u)));\n";
+                }
+                o << "#else\n"
                      "    const bool flo_ = (par_ & 0x8000u) && (klo_ & 15u) == ln.br;\n"
                      "    const bool fhi_ = (par_ & 0x80000000u) && (khi_ & 15u) == ln.br;\n";
                 if (n <= 16) {
@@ -459,6 +476,7 @@ struct Gen {
                           << "u ? 1u << (ilo_ & 15u) : 0u) | (fhi_ && (ihi_ >> 4) == " << k
                           << "u ? 0x10000u << (ihi_ & 15u) : 0u);\n";
                 }
+                o << "#endif\n";
             }
             o << "  }\n";
             break;
@@ -554,8 +572,18 @@ struct Gen {
           << "    tab8_[t_] = (unsigned char)v_; tabm_[t_] = (unsigned char)(v_ & QMAG); tabs_[t_] = (unsigned char)(v_ >> 7); }\n"
           << "  __syncthreads();\n"
           << "  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: SGPR batch indices\n"
+          // Frame counts and indices in 32 bits, unsigned: a decode is at most 2^31 - 8 frames
+          // (polar_sc_host.cpp decode_common), so wave * 8 + 7 fits, and every clamp and bound on
+          // them is a scalar instruction; the 64-bit signed compares of the former form have no
+          // scalar encoding and ran on the vector ALU, with a 64-bit add per address.
+          // (-DPOLAR_MASK_ADDR64: that form, for A/Bs)
+          << "#ifndef POLAR_MASK_ADDR64\n"
+          << "  const u32 nw_ = ((u32)batch + 7u) >> 3;\n"
+          << "  const u32 wave = blockIdx.x * " << wpb << "u + (u32)wib;\n"
+          << "#else\n"
           << "  const long nw_ = ((long)batch + 7) / 8;\n"
           << "  long wave = (long)blockIdx.x * " << wpb << " + wib;\n"
+          << "#endif\n"
           << "  if (wave >= nw_) return;\n"
           << "  unsigned char *st_ = (unsigned char *)stage_ + wib * " << 8 * FS << ";\n"
           << "  const bool al_ = (((unsigned long)llr) & 15u) == 0u;\n"
@@ -565,6 +593,19 @@ struct Gen {
           // loads, and branch-free -- a branch in the middle of the straight-line decode costs
           // the register allocator ~100 VGPRs. lla_: the input rounded down to 16 bytes (an
           // unaligned input is byte-copied instead and the async rows are overwritten).
+          // The frame address is a uniform 64-bit base, the lane's 16-byte chunk a 32-bit offset
+          // next to it (the load's SGPR-base form, as the pair kernel addresses everything).
+          << "#ifndef POLAR_MASK_ADDR64\n"
+          << "  auto fetch_ = [&](u32 w, int lane) {\n"
+          << "    const u32 f0_ = w * 8u, fl_ = (u32)batch - 1u, lo_ = (u32)lane * 16u;\n";
+        for (int f = 0; f < 8; f++)
+            for (int c = 0; c < (LPF + 63) / 64; c++)
+                o << "    { const u32 fr_ = (u32)__builtin_amdgcn_readfirstlane((int)__builtin_elementwise_min(f0_ + " << f
+                  << "u, fl_));\n"
+                  << "      if (" << (LPF - c * 64 >= 64 ? std::string("true") : "lane < " + std::to_string(LPF - c * 64))
+                  << ") __builtin_amdgcn_global_load_lds((gas_t)(lla_ + ((size_t)fr_ * " << N << " + " << c * 1024
+                  << ") + (size_t)lo_), (las_t)(st_ + " << f * FS + c * 1024 << "), 16, 0, 0); }\n";
+        o << "  };\n#else\n"
           << "  auto fetch_ = [&](long w, int lane) {\n"
           << "    const long f0_ = w * 8;\n";
         for (int f = 0; f < 8; f++)
@@ -584,7 +625,7 @@ struct Gen {
         // Lane-derived values are recomputed after the fetch (the empty asm makes the lane
         // index opaque): kept from the top they would stay live across the whole decode
         // (~30 VGPRs, 4 -> 3 waves per SIMD).
-        o << "  };\n"
+        o << "  };\n#endif\n"
           << "  {\n"
           << "  int lane = threadIdx.x & 63;\n"
           << "  asm volatile(\"\" : \"+v\"(lane));\n"
@@ -609,15 +650,33 @@ struct Gen {
         root_presplit(G);
         all_ops();
         // END (my_module.h:1848-1869) + wrapper_out: x^ words in natural order
-        o << "  const long f_lo = wave * 8 + (lane >> 4), f_hi = f_lo + 4;\n"
+        // The rows of frames wave * 8 and wave * 8 + 4 are uniform bases (SGPRs); a lane adds one
+        // 32-bit byte offset, its row inside the four and its word (out_stride is the plan's G
+        // or G rounded up to 4, polar_sc_host.cpp). The store predicates compare the row with the
+        // number of frames the batch has left for this wave. (-DPOLAR_MASK_ADDR64: a 64-bit
+        // pointer and frame index per lane)
+        o << "#ifndef POLAR_MASK_ADDR64\n"
+          << "  const u32 nf_ = (u32)batch - wave * 8u;\n"
+          << "  const bool st_lo = (u32)row < nf_, st_hi = (u32)row + 4u < nf_;\n"
+          << "  unsigned short *const o_lo = out + (size_t)(wave * 8u) * (u32)out_stride, *const o_hi = o_lo + 4 * (size_t)(u32)out_stride;\n"
+          // (in bytes: doubled after the widening it would be a 64-bit shift and add per store)
+          << "  const u32 lw_ = ((u32)row * (u32)out_stride + (u32)pl) * 2u;\n"
+          << "#define POLAR_OUT(o, w) *(unsigned short *)((char *)(o + (w)) + lw_)\n"
+          << "#define POLAR_OUTV(o, w) *(unsigned short *)((char *)(o) + (lw_ + (u32)(w) * 2u))\n"
+          << "#else\n"
+          << "  const long f_lo = wave * 8 + (lane >> 4), f_hi = f_lo + 4;\n"
           << "  const bool st_lo = f_lo < batch, st_hi = f_hi < batch;\n"
-          << "  unsigned short *o_lo = out + (size_t)f_lo * out_stride, *o_hi = out + (size_t)f_hi * out_stride;\n";
+          << "  unsigned short *o_lo = out + (size_t)f_lo * out_stride + pl, *o_hi = out + (size_t)f_hi * out_stride + pl;\n"
+          << "#define POLAR_OUT(o, w) o[w]\n#define POLAR_OUTV(o, w) o[w]\n"
+          << "#endif\n";
         for (int c = 0; c < (G + 15) / 16; c++) {
-            o << "  { const u32 t_ = row_transpose16(to_position_order(" << get16(16 * c) << ", ln), ln); const int w_ = " << 16 * c << " + pl;\n"
-              << "    if (w_ < " << G << ") { if (st_lo) o_lo[w_] = (unsigned short)(t_ & 0xFFFFu); "
-              << "if (st_hi) o_hi[w_] = (unsigned short)(t_ >> 16); } }\n";
+            o << "  { const u32 t_ = row_transpose16(to_position_order(" << get16(16 * c) << ", ln), ln);\n"
+              << "    if (" << 16 * c << " + pl < " << G << ") { if (st_lo) POLAR_OUT(o_lo, " << 16 * c
+              << ") = (unsigned short)(t_ & 0xFFFFu); if (st_hi) POLAR_OUT(o_hi, " << 16 * c
+              << ") = (unsigned short)(t_ >> 16); } }\n";
         }
-        o << "  for (int w_ = " << G << " + pl; w_ < out_stride; w_ += 16) { if (st_lo) o_lo[w_] = 0; if (st_hi) o_hi[w_] = 0; }\n"
+        o << "  for (int w_ = " << G << "; w_ + pl < out_stride; w_ += 16) { if (st_lo) POLAR_OUTV(o_lo, w_) = 0; "
+          << "if (st_hi) POLAR_OUTV(o_hi, w_) = 0; }\n"
           << "  }\n";
         o << "}\n";
         return o.str();

@@ -13,6 +13,15 @@ VALU count of one frame pair's (or frame's) subtree work -- the serial instructi
 long-block decode.
 
     python tools/pair_census.py [--mask frozen_n_262144_k_131072] [--tuning k=v,...]
+
+--cycles (per-mask kernels): every VALU instruction weighted by the issue cost of its form at the
+plan's occupancy (DESIGN.md 3.0, the table below), per op class with the costliest mnemonics;
+forms the microbenchmark has not measured are listed as unpriced, with their count, not guessed.
+--no-rep-fallback leaves the exact REP fallback bodies out (they run only when a REP total is 0),
+so that the count tracks the executed stream; --defines builds another form of the kernel
+(-DPOLAR_... switches) for comparison.
+
+    python tools/pair_census.py --mask FB_N1024_K512 --cycles --no-rep-fallback [--defines POLAR_PM1_MASK,...]
 """
 import argparse
 import collections
@@ -27,6 +36,136 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 CSRC = os.path.join(ROOT, "sc_polar_decoder_hls_amd", "csrc")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+
+# ---- issue cost per instruction form: SIMD cycles per wave64 instruction at
+# 1 / 2 / 4 / 8 waves per SIMD, tools/valu_microbench.hip (profiles/r02_valu_microbench.log,
+# r04_valu_microbench_{encoding,forms}.log, r08_valu_microbench_forms.log)
+WAVES = (1, 2, 4, 8)
+DUAL = (4.8, 2.4, 1.97, 1.45)        # 32- / 16-bit VOP1 / VOP2, VGPR, inline or literal operands (also as _e64)
+SINGLE = (5.2, 4.45, 3.25, 2.62)     # v_pk_*, DPP, 3-source VOP3, v_lshlrev_b32, v_min_u32, VOP2 with an SGPR operand
+BITOP3 = (5.2, 4.05, 2.93, 2.33)
+PERMSWAP = (8.8, 8.3, 6.3, 5.1)
+CNDMASK_VCC = (19.0, 16.0, 12.6, 10.7)
+DUAL_OPS = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_lshrrev_b32",
+            "v_ashrrev_i32", "v_not_b32", "v_min_u16", "v_add_u16", "v_max_i16", "v_add_f32", "v_mov_b32"}
+SINGLE_OPS = {"v_bfi_b32", "v_perm_b32", "v_or3_b32", "v_and_or_b32", "v_lshl_or_b32", "v_min3_u32", "v_lshlrev_b32",
+              "v_min_u32", "v_cndmask_b32_e64"}
+# forms measured for this census (profiles/r08_valu_microbench_forms.log), by mnemonic without its
+# encoding suffix. v_cmp_*: the same for a 32- and a 64-bit compare, VCC or SGPR-pair destination,
+# VGPR or SGPR operand.
+CMP = (8.5, 4.25, 3.99, 2.95)
+MEASURED = {
+    "v_lshl_add_u64": (5.28, 4.52, 3.27, 2.64), "v_lshlrev_b64": (5.15, 4.45, 3.24, 2.62),
+    "v_mad_u32_u24": (5.20, 4.46, 3.25, 2.62), "v_mul_u32_u24": (4.83, 4.35, 3.18, 2.59),
+    "v_mul_i32_i24": (4.83, 4.35, 3.18, 2.59), "v_bfe_u32": (5.14, 4.45, 3.24, 2.62),
+    "v_add3_u32": (5.20, 4.46, 3.25, 2.62), "v_xad_u32": (5.20, 4.46, 3.25, 2.62),
+    "v_lshl_add_u32": (5.20, 4.46, 3.25, 2.62),
+}
+
+
+def form_cost(line):
+    """(form name, cost tuple or None) of one VALU instruction line of the assembly"""
+    m = re.match(r"^\s+(v_\w+)\s*(.*)$", line)
+    ins, ops = m.group(1), m.group(2).split(";")[0]
+    base = re.sub(r"_(e32|e64|dpp|sdwa)$", "", ins)
+    if ins in MEASURED or base in MEASURED:
+        return ins if ins in MEASURED else base, MEASURED.get(ins, MEASURED.get(base))
+    if ins.endswith("_sdwa"):
+        return ins, None
+    if re.match(r"v_cmp_\w+_[iuf]\d+$", base):
+        return ins, CMP
+    if ins.endswith("_dpp") or "row_" in ops or "quad_perm" in ops:
+        return base + "_dpp", SINGLE
+    if ins == "v_cndmask_b32_e32":
+        return ins, CNDMASK_VCC
+    if base in ("v_bitop3_b32", "v_fma_f32"):
+        return base, BITOP3
+    if base in ("v_permlane16_swap_b32", "v_permlane32_swap_b32"):
+        return base, PERMSWAP
+    if base.startswith("v_pk_"):
+        return base, SINGLE
+    if ins in SINGLE_OPS or base in SINGLE_OPS:
+        return base if base in SINGLE_OPS else ins, SINGLE
+    if base in DUAL_OPS:
+        srcs = ops.split(",")[1:]
+        if any(re.match(r"\s*(s\d+|s\[|vcc|exec|m0)", o) for o in srcs):
+            return base + " (sgpr operand)", SINGLE
+        return base, DUAL
+    return ins, None
+
+
+def drop_rep_fallback(src):
+    """the generated source without the exact REP chains (taken only when a REP total is 0): the
+    test and the branch stay (the asm comment keeps the emptied body from becoming a select)"""
+    return re.sub(r"(    if \(rep_any_zero\(acc_\)\) \{\n      acc_ = 0u;\n)(?:      acc_ = G_sm<REPSAT>.*\n)+",
+                  r'\1      asm volatile("; exact REP chain left out");\n', src)
+
+
+def drop_unaligned_copy(src):
+    """the per-mask kernel's source without the byte copy of an input that is not 16-byte aligned"""
+    return re.sub(r"  if \(!al_\) \{.*?\n  \}\n", "", src, count=1, flags=re.S)
+
+
+def mask_cycles(asm, waves=4):
+    """per op class of the per-mask kernel: {class: {form: [count, cost or None]}}"""
+    col = WAVES.index(waves)
+    out = collections.defaultdict(lambda: collections.defaultdict(lambda: [0, None]))
+    cur, cls = False, "prologue"
+    for line in asm.split("\n"):
+        if re.match(r"^polar_sc_mask_kernel:", line):
+            cur = True
+            continue
+        if not cur:
+            continue
+        if re.match(r"^\.Lfunc_end", line):
+            break
+        m = re.match(r"^\s*;@@ (.*)$", line)
+        if m:
+            cls = m.group(1).strip()
+            continue
+        if re.match(r"^\s+v_\w+", line):
+            form, cost = form_cost(line)
+            e = out[cls][form]
+            e[0] += 1
+            e[1] = cost[col] if cost else None
+    return out
+
+
+def cycles_census(src, waves=4, defines=(), no_rep_fallback=False):
+    """cost-weighted census of a per-mask kernel source: (total priced cycles, priced VALU,
+    {unpriced form: count}, per-class table)"""
+    if no_rep_fallback:
+        src = drop_rep_fallback(src)
+    marked, _ = mark_mask_kernel(src)
+    with tempfile.TemporaryDirectory() as tmp:
+        table = mask_cycles(compile_asm(marked, tmp, ["-D" + d for d in defines]), waves)
+    total, priced, unpriced = 0.0, 0, collections.Counter()
+    for forms in table.values():
+        for form, (n, c) in forms.items():
+            if c is None:
+                unpriced[form] += n
+            else:
+                total += n * c
+                priced += n
+    return total, priced, dict(unpriced), table
+
+
+def print_cycles(name, waves, res):
+    total, priced, unpriced, table = res
+    print("%s: per-mask kernel at %d waves per SIMD: %d priced VALU, %.0f issue cycles per wave; unpriced VALU %d"
+          % (name, waves, priced, total, sum(unpriced.values())))
+    print("%-12s %7s %9s %6s  %s" % ("class", "VALU", "cycles", "%", "costliest forms (count x cycles)"))
+    rows = []
+    for cls, forms in table.items():
+        cyc = sum(n * c for n, c in forms.values() if c is not None)
+        top = sorted(((n * c, f, n, c) for f, (n, c) in forms.items() if c is not None), reverse=True)[:4]
+        rows.append((cyc, cls, sum(n for n, _ in forms.values()), top))
+    for cyc, cls, n, top in sorted(rows, reverse=True):
+        print("%-12s %7d %9.0f %5.1f%%  %s" % (cls, n, cyc, 100.0 * cyc / max(total, 1.0),
+                                               ", ".join("%s %d x %.2f" % (f, k, c) for _, f, k, c in top)))
+    for f, n in sorted(unpriced.items(), key=lambda kv: -kv[1]):
+        print("unpriced     %7d            %s" % (n, f))
+
 
 OPLINE = re.compile(r"^(\s*)(?:u32 x\d+_;\n\s*)?\{ // (.*)$|^(\s*)const u32 (x\d+_) = .*// (H0? n \d)$")
 
@@ -125,13 +264,13 @@ def mark(src):
     return "\n".join(out), n
 
 
-def compile_asm(src, tmp):
+def compile_asm(src, tmp, extra=()):
     path = os.path.join(tmp, "k.hip")
     with open(path, "w") as f:
         f.write("#include <hip/hip_runtime.h>\n" + src)
     s = os.path.join(tmp, "k.s")
     subprocess.run([CLANG, "-x", "hip", "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-std=c++17", "-w",
-                    "-I", CSRC, "-S", "-o", s, path], check=True)
+                    "-I", CSRC, "-S", "-o", s, path] + list(extra), check=True)
     return open(s).read()
 
 
@@ -171,6 +310,10 @@ def main():
     ap.add_argument("--tuning", default="")
     ap.add_argument("--source", help="census of this generated source file instead of the plan's")
     ap.add_argument("--config", default="", help="polar_sc_config fields, e.g. sigmag=0,par=64")
+    ap.add_argument("--cycles", action="store_true", help="per-mask kernel: VALU weighted by the issue cost of its form")
+    ap.add_argument("--waves", type=int, default=4, choices=WAVES, help="waves per SIMD the costs are taken at")
+    ap.add_argument("--no-rep-fallback", action="store_true", help="leave the exact REP fallback bodies out")
+    ap.add_argument("--defines", default="", help="comma-separated macros for the compile, e.g. POLAR_PM1_MASK")
     args = ap.parse_args()
     import sc_polar_decoder_hls_amd as pkg
     import util
@@ -182,10 +325,16 @@ def main():
             setattr(cfg, kv.split("=")[0], int(kv.split("=")[1]))
     dec = pkg.Decoder(util.mask(args.mask), config=cfg, tuning=tun or None)
     src = open(args.source).read() if args.source else dec.kernel_source()
+    defines = [d for d in args.defines.split(",") if d]
+    if "polar_sc_mask_kernel(" in src and args.cycles:
+        print_cycles(args.mask, args.waves, cycles_census(src, args.waves, defines, args.no_rep_fallback))
+        return
     if "polar_sc_mask_kernel(" in src:   # per-mask kernel: one straight-line function
+        if args.no_rep_fallback:
+            src = drop_rep_fallback(src)
         marked, nmark = mark_mask_kernel(src)
         with tempfile.TemporaryDirectory() as tmp:
-            tot_v, tot_a = mask_census(compile_asm(marked, tmp))
+            tot_v, tot_a = mask_census(compile_asm(marked, tmp, ["-D" + d for d in defines]))
         nv = sum(tot_v.values())
         print("%s: per-mask kernel, %d op markers; VALU per wave %d, all instructions %d"
               % (args.mask, nmark, nv, sum(tot_a.values())))

@@ -18,8 +18,9 @@
 #define REP8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 
 template <int OP>
-__device__ __forceinline__ void op(unsigned &r, unsigned k)
+__device__ __forceinline__ void op(unsigned &r, unsigned long long &q, unsigned k)
 {
+    const unsigned long long k64 = ((unsigned long long)k << 32) | k;   // (64-bit operand forms)
     if constexpr (OP == 0) asm volatile("v_add_u32 %0, %0, %1" : "+v"(r) : "v"(k));
     if constexpr (OP == 1) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(r) : "v"(k));
     if constexpr (OP == 2) asm volatile("v_pk_add_u16 %0, %0, %1" : "+v"(r) : "v"(k));
@@ -68,6 +69,23 @@ __device__ __forceinline__ void op(unsigned &r, unsigned k)
     if constexpr (OP == 41) asm volatile("v_pk_sub_u16 %0, %0, %1" : "+v"(r) : "v"(k));
     if constexpr (OP == 42) asm volatile("v_sub_u32_e64 %0, %0, %1" : "+v"(r) : "v"(k));
     if constexpr (OP == 43) asm volatile("v_max_i16_e32 %0, %0, %1" : "+v"(r) : "v"(k));
+    // the forms the cost-weighted census prices (tools/pair_census.py --cycles): compares with a
+    // VCC and an SGPR-pair destination, 32- and 64-bit; 64-bit address arithmetic; 24-bit multiplies
+    if constexpr (OP == 44) asm volatile("v_cmp_eq_u32_e32 vcc, %0, %1" : : "v"(r), "v"(k) : "vcc");
+    if constexpr (OP == 45) asm volatile("v_cmp_eq_u32_e64 s[4:5], %0, %1" : : "v"(r), "v"(k) : "s4", "s5");
+    if constexpr (OP == 46) asm volatile("v_cmp_lt_i64_e32 vcc, %0, %1" : : "v"(q), "v"(k64) : "vcc");
+    if constexpr (OP == 47) asm volatile("v_cmp_lt_i64_e64 s[4:5], %0, %1" : : "v"(q), "v"(k64) : "s4", "s5");
+    if constexpr (OP == 48) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(q) : "v"(k64));
+    if constexpr (OP == 49) asm volatile("v_mad_u32_u24 %0, %0, %1, %1" : "+v"(r) : "v"(k));
+    if constexpr (OP == 50) asm volatile("v_mul_u32_u24_e32 %0, %0, %1" : "+v"(r) : "v"(k));
+    if constexpr (OP == 51) asm volatile("v_cndmask_b32_e64 %0, %0, %1, vcc" : "+v"(r) : "v"(k));
+    if constexpr (OP == 52) asm volatile("v_mul_i32_i24_e32 %0, %0, %1" : "+v"(r) : "v"(k));
+    if constexpr (OP == 53) asm volatile("v_lshlrev_b64 %0, 1, %0" : "+v"(q));
+    if constexpr (OP == 55) asm volatile("v_bfe_u32 %0, %0, 3, 5" : "+v"(r));
+    if constexpr (OP == 56) asm volatile("v_add3_u32 %0, %0, %1, %1" : "+v"(r) : "v"(k));
+    if constexpr (OP == 57) asm volatile("v_xad_u32 %0, %0, %1, %1" : "+v"(r) : "v"(k));
+    if constexpr (OP == 58) asm volatile("v_lshl_add_u32 %0, %0, 3, %1" : "+v"(r) : "v"(k));
+    if constexpr (OP == 54) asm volatile("v_cmp_gt_u32_e32 vcc, %1, %0" : : "v"(r), "s"(k) : "vcc");
 }
 static const char *names[] = {"v_add_u32", "v_xor_b32", "v_pk_add_u16", "v_pk_min_u16", "v_bitop3_b32",
                               "v_mov_b32_dpp row_ror", "v_add_u32_dpp row_ror", "v_and_or_b32",
@@ -81,16 +99,25 @@ static const char *names[] = {"v_add_u32", "v_xor_b32", "v_pk_add_u16", "v_pk_mi
                               "v_min_u32_e32", "v_min_u16_e32", "v_add_u16_e32", "v_cndmask_b32_e64 sgpr mask",
                               "v_lshl_or_b32", "v_and_b32_e32 inline 15", "v_xor_b32_e32 literal",
                               "v_add_u32_e32 inline 5", "v_permlane16_swap_b32", "v_mov_b32_e32 vgpr",
-                              "v_ashrrev_i32_e32 vgpr", "v_pk_sub_u16", "v_sub_u32_e64 (VOP3)", "v_max_i16_e32"};
-constexpr int NOPS = 44;
+                              "v_ashrrev_i32_e32 vgpr", "v_pk_sub_u16", "v_sub_u32_e64 (VOP3)", "v_max_i16_e32",
+                              "v_cmp_eq_u32_e32 vcc", "v_cmp_eq_u32_e64 sgpr pair", "v_cmp_lt_i64_e32 vcc",
+                              "v_cmp_lt_i64_e64 sgpr pair", "v_lshl_add_u64", "v_mad_u32_u24", "v_mul_u32_u24_e32",
+                              "v_cndmask_b32_e64 vcc mask", "v_mul_i32_i24_e32", "v_lshlrev_b64",
+                              "v_cmp_gt_u32_e32 vcc, sgpr operand", "v_bfe_u32", "v_add3_u32", "v_xad_u32",
+                              "v_lshl_add_u32"};
+constexpr int NOPS = 59;
 
 // CHAINS independent accumulators per wave; stamps[wave] = {memtime delta, memrealtime delta}
 template <int OP, int CHAINS>
 __global__ void __launch_bounds__(256) bench(unsigned *out, unsigned long long *stamps, int iters)
 {
     unsigned r[8];
+    unsigned long long q[8];
 #pragma unroll
-    for (int c = 0; c < 8; c++) r[c] = threadIdx.x * (2 * c + 3);
+    for (int c = 0; c < 8; c++) {
+        r[c] = threadIdx.x * (2 * c + 3);
+        q[c] = ((unsigned long long)(c + 1) << 32) | r[c];
+    }
     const unsigned k = 0x01230123u;
     __syncthreads();
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), w0 = __builtin_amdgcn_s_memrealtime();
@@ -100,13 +127,13 @@ __global__ void __launch_bounds__(256) bench(unsigned *out, unsigned long long *
 #pragma unroll
         for (int rep = 0; rep < 64 / CHAINS; rep++) {
 #pragma unroll
-            for (int c = 0; c < CHAINS; c++) op<OP>(r[c], k);
+            for (int c = 0; c < CHAINS; c++) op<OP>(r[c], q[c], k);
         }
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), w1 = __builtin_amdgcn_s_memrealtime();
     unsigned x = 0;
 #pragma unroll
-    for (int c = 0; c < 8; c++) x ^= r[c];
+    for (int c = 0; c < 8; c++) x ^= r[c] ^ (unsigned)q[c] ^ (unsigned)(q[c] >> 32);
     out[blockIdx.x * 256 + threadIdx.x] = x;
     if ((threadIdx.x & 63) == 0) {
         const int w = blockIdx.x * 4 + (threadIdx.x >> 6);

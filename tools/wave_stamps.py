@@ -131,7 +131,7 @@ def build(out_name="wave_stamps", src=None):
     first = "  __builtin_amdgcn_sched_barrier(0);\n  { // F level 0"
     assert first in src
     src = src.replace(first, stamp % 2 + first, 1)
-    outp = "  const long f_lo = wave * 8"
+    outp = "#ifndef POLAR_MASK_ADDR64\n  const u32 nf_ ="   # (the output section's first line)
     assert outp in src
     src = src.replace(outp, stamp % 3 + outp, 1)
     tail = "  }\n}\n"
