@@ -364,6 +364,7 @@ def all_items():
     # generated kernels (one code object per mask and configuration); the interpreter formats
     # share one per format
     items += sweep_items() + ca2_items() + q9_items() + par48_gpu_items() + high_rate_items() + issue_form_items()
+    items += leaf_block_items()
     return items
 
 
@@ -374,6 +375,34 @@ def wide_spc_mask():
     m[1024:2048] = 1
     m[1024] = 0
     return m
+
+
+# ---- REP / SPC sub-blocks of the leaf inside a PAR 32 / 64 word (tests/test_leaf_blocks_gpu.py):
+# the last 16-LLR word of a PAR word sees magnitudes up to QMAG * PAR / 16 (exact G above it), so
+# its blocks at B = 8 / 12 reach the largest values a block decoder can meet ----------------------
+LEAF_BLOCK_WORDS = ("0000000100010111", "0000000101110001", "0001011100000001", "0000000101111111",
+                    "0001000100010001", "0111011101110111")   # (position 0 first)
+LEAF_BLOCK_FORMATS = ((64, 9), (64, 6), (32, 9), (64, 8))     # (PAR, LLR_BITS), SIGMAG, EXTENDED 1
+
+
+def leaf_block_mask(par):
+    """N = 2048: in every second PAR word the last 16-LLR word holds one of LEAF_BLOCK_WORDS; the
+    words before it are all frozen (the last word then sees the exact sum of all of them), all
+    information, or as the rate-1/2 code has them"""
+    m = mask("frozen_n_2048_k_1024").copy()
+    for i, g in enumerate(range(0, 2048 // par, 2)):
+        w = m[par * g:par * (g + 1)]
+        w[par - 16:] = [int(c) for c in LEAF_BLOCK_WORDS[i % len(LEAF_BLOCK_WORDS)]]
+        if i % 3 == 0:
+            w[:par - 16] = 0
+        elif i % 3 == 1:
+            w[:par - 32] = 0
+    return m
+
+
+def leaf_block_items():
+    return [("leaf_blocks_p%d_q%d" % (par, q), leaf_block_mask(par), {"par": par, "llr_bits": q}, {"kernel": 3})
+            for par, q in LEAF_BLOCK_FORMATS]
 
 
 def issue_form_items():

@@ -190,6 +190,7 @@ struct Lanes {
     u32 pl;               // physical lane in the row, 0..15
     u32 pos;              // word position held by this lane (lane_pos(pl))
     u32 br;               // bitrev4(pos)
+    u32 nbr;              // 15 - br in both halves: the tie nibble of the SPC sub-block keys (leaf_ms)
     template <int H> __device__ __forceinline__ u32 amask() const
     {
         if constexpr (H == 1) return a1;
@@ -202,6 +203,7 @@ struct Lanes {
         pl = p;
         pos = lane_pos(p);
         br = ((pos & 1u) << 3) | ((pos & 2u) << 1) | ((pos & 4u) >> 1) | ((pos & 8u) >> 3);
+        nbr = (15u - br) * 0x00010001u;
         a1 = clear_mask<0>(pos);
         a2 = clear_mask<1>(pos);
         a4 = clear_mask<2>(pos);
@@ -435,7 +437,60 @@ __device__ __forceinline__ u32 sm8_pair(u32 lo, u32 hi)
 //       partial sums as masks), |a| < |b| from M' - M, magnitude = x ? |M' - M| : M' + M,
 //       sign = S ^ (x & ~lt)   (same signs -> sign(b); differ -> lt ? sign(b) : sign(a'))
 // Returns x as 16-bit masks (0xFFFF = bit 1).
+//
+// Sub-blocks of width 4 and 8 that are an SPC (only the first position frozen) or a REP (only
+// the last position carries information) are decided directly, with the bits the recursion
+// gives when the G inside the leaf is exact (EXTENDED = 1), where the block's
+// magnitude bound fits the packed halves (LeafBlock):
+//   SPC: x = the signs; on odd parity the position of the smallest magnitude flips, among equal
+//        magnitudes the one with the largest bit-reversed index in the block (the opposite tie
+//        order from the node-level leaf_spc; bitrev4 of the word position orders an aligned
+//        block's positions as the block's own bit reversal does).
+//   REP: every left child is all frozen, so each level is the exact sign-magnitude add
+//        a + b whose zero keeps the sign of a. The first lane of the block sees, in a butterfly
+//        at distance W/2 .. 1, the sums of the positions = 0 mod W/2, .. mod 2, mod 1; x is the
+//        sign of the last of them that is not 0, and the sign bit of position 0 if all are.
+//        Carried as a mask m: m' = (sum + m < 0).
+// (-DPOLAR_LEAF_RECURSE: the recursion for these blocks too, for A/Bs)
 // ---------------------------------------------------------------------------------------
+#ifndef POLAR_LEAF_RECURSE
+constexpr bool LEAF_BLOCKS = EXT;
+#else
+constexpr bool LEAF_BLOCKS = false;
+#endif
+// what the packed 16-bit halves of the two block decoders rely on; a block whose bound misses
+// it takes the recursion
+template <int W>
+struct LeafBlock {
+    // a leaf's inputs: stage values (<= QMAG) at PAR <= 16; inside a PAR 32 / 64 word the exact
+    // G above the 16-LLR words (G_split_x / the unclamped GLEAF of par_expand) doubles them per
+    // level, up to QMAG * P16 in the last word. Each exact G inside the leaf doubles again.
+    static constexpr u32 MMAX = QMAG * (u32)P16 * 16u / (u32)W;
+    // SPC key (|lambda| << 4) | nibble: the difference of two keys has to keep its sign in 16 bits
+    static constexpr bool SPC_OK = ((MMAX << 4) | 15u) < 0x8000u;
+    // REP values BIAS +- |lambda| stay positive, also with the carried -1; W of them do not carry
+    // into the other half, and sum + m keeps its sign in 16 bits
+    static constexpr u32 BIAS = (1u << (QB + 2)) * (u32)P16;
+    static constexpr bool REP_OK = BIAS > MMAX + 1u && (u32)W * (BIAS + MMAX) < 0x10000u && (u32)W * MMAX + 1u < 0x8000u;
+};
+static_assert(P16 > 1 || (LeafBlock<4>::SPC_OK && LeafBlock<8>::SPC_OK && LeafBlock<4>::REP_OK && LeafBlock<8>::REP_OK),
+              "PAR <= 16: both block decoders at every LLR_BITS 5..9");
+// the lane that holds word position p (lane_pos is an involution)
+constexpr u32 lane_of_pos(u32 p) { return POLAR_LANE_REMAP ? (p ^ ((p & 4u) ? 3u : 0u)) : p; }
+// lane L of the row to all 16 (row_newbcast)
+template <u32 L>
+__device__ __forceinline__ u32 row_bcast(u32 v)
+{
+    return __builtin_amdgcn_update_dpp(0u, v, 0x150 + (int)L, 0xF, 0xF, true);
+}
+// one REP level: partial sums at distance H (K-th level, offset BIAS << K) and the carried sign
+template <int W, int H, int K>
+__device__ __forceinline__ void rep_level(u32 &v, u32 &m)
+{
+    v += xorlane<H>(v);
+    m = pk_sra(pk_sub(pk_add(v, m), (LeafBlock<W>::BIAS << K) * 0x00010001u), 15);
+}
+
 template <u32 FB, int B, int W>
 __device__ __forceinline__ u32 leaf_ms(u32 M, u32 S, const Lanes &ln)
 {
@@ -445,6 +500,30 @@ __device__ __forceinline__ u32 leaf_ms(u32 M, u32 S, const Lanes &ln)
         return 0u;
     } else if constexpr (sub == bm) {
         return S;
+    } else if constexpr (LEAF_BLOCKS && (W == 4 || W == 8) && LeafBlock<W>::SPC_OK && sub == (bm & ~(1u << B))) {
+        u32 par = S;
+        if constexpr (W == 8) par ^= xorlane<4>(par);
+        par ^= xorlane<2>(par);
+        par ^= xorlane<1>(par);
+        const u32 k0 = pk_mad_u16(M, 0x00100010u, ln.nbr);
+        u32 k = k0;
+        if constexpr (W == 8) k = pk_min(k, xorlane<4>(k));
+        k = pk_min(k, xorlane<2>(k));
+        k = pk_min(k, xorlane<1>(k));
+        // k <= k0, equal only on the lane of the minimum (the nibbles differ inside a block)
+        return S ^ (par & ~opaque(pk_sra(pk_sub(k, k0), 15)));
+    } else if constexpr (LEAF_BLOCKS && (W == 4 || W == 8) && LeafBlock<W>::REP_OK && sub == (1u << (B + W - 1))) {
+        u32 v = pk_mad_u16(M, S | 0x00010001u, LeafBlock<W>::BIAS * 0x00010001u);
+        u32 m = S;
+        if constexpr (W == 8) {
+            rep_level<W, 4, 1>(v, m);
+            rep_level<W, 2, 2>(v, m);
+            rep_level<W, 1, 3>(v, m);
+        } else {
+            rep_level<W, 2, 1>(v, m);
+            rep_level<W, 1, 2>(v, m);
+        }
+        return row_bcast<lane_of_pos(B)>(m);
     } else if constexpr (W == 2) {
         if constexpr ((sub >> B) == 1u) {
             return (S ^ xorlane<1>(S)) & ln.a1;                 // (1, 0): x = [sa ^ sb, 0]

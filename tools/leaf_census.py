@@ -10,7 +10,10 @@ at (B, W) is its kernel's count minus its two children's (W = 2: the whole base 
 instruction of the full leaf is attributed to exactly one node; the per-level totals add up to
 the W = 16 kernel's count up to the scheduler's reshuffling across nodes (reported as `slack`).
 
-    python tools/leaf_census.py [--mask FB_N1024_K512] [--config sigmag=0]
+    python tools/leaf_census.py [--mask FB_N1024_K512] [--ca2] [--defines POLAR_LEAF_RECURSE] [--patterns]
+
+--defines builds another form of the leaf (-DPOLAR_... switches, e.g. POLAR_LEAF_RECURSE: REP and SPC
+sub-blocks by the recursion too); --patterns lists the whole-leaf count of every distinct pattern.
 """
 import argparse
 import collections
@@ -96,7 +99,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mask", default="FB_N1024_K512")
     ap.add_argument("--ca2", action="store_true", help="the CA2 leaf (leaf_ca2, no MIN)")
+    ap.add_argument("--defines", default="", help="comma-separated macros for the compile, e.g. POLAR_LEAF_RECURSE")
+    ap.add_argument("--patterns", action="store_true", help="also list the whole-leaf VALU of every distinct pattern")
     args = ap.parse_args()
+    defines = ["-D" + d for d in args.defines.split(",") if d]
     import sc_polar_decoder_hls_amd as pkg
     import util
     cfg = None
@@ -112,7 +118,7 @@ def main():
         open(path, "w").write(src)
         s = os.path.join(tmp, "k.s")
         subprocess.run([CLANG, "-x", "hip", "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-std=c++17", "-w",
-                        "-I", CSRC, "-S", "-o", s, path], check=True)
+                        "-I", CSRC, "-S", "-o", s, path] + defines, check=True)
         per = census(open(s).read())
     by_level = {W: collections.Counter() for W in (16, 8, 4, 2)}
     whole = collections.Counter()
@@ -140,6 +146,11 @@ def main():
         print("%-8s %8.1f " % ("W=%d" % W, n / nleaf) + " ".join("%10.1f" % (c[x] / nleaf) for x in cols))
     print("%-8s %8.1f " % ("all", tot / nleaf) + " ".join("%10.1f" % (whole[x] / nleaf) for x in cols))
     print("slack (whole - sum of nodes) per leaf: %.1f" % ((tot - acc) / nleaf))
+    if args.patterns:
+        print("pattern (position 0 first)  records  VALU")
+        for fb in sorted(mult, key=lambda f: -sum(per["k_%04x_0_16" % f].values())):
+            print("%s  %7d  %4d" % ("".join(str((fb >> i) & 1) for i in range(16)), mult[fb],
+                                    sum(per["k_%04x_0_16" % fb].values())))
 
 
 if __name__ == "__main__":
