@@ -59,6 +59,42 @@ bool jit_supported(uint32_t N) { return N >= 32 && N <= 1024; }
 
 namespace {
 
+// REP nodes whose total is 0 (the REP case of Gen::op). The decision of a node of n words is the
+// sign of acc = sat(T_{n-1} + sat(... sat(T_0 + 0))) with T_w the exact pair-tree sum of word w
+// (row_add_tree: positions (j, j + 8), then distance 4, 2, 1, the lower position as operand a; a
+// zero result takes the sign of a), and the accumulate step G_sm<REPSAT>(a = T_w, b = acc). A
+// total that is not 0 has its numeric sign, which the two's complement chain carries. A total of
+// 0 takes the sign of T_{n-1}; if that is 0, the sign of the last non-zero of the sums of the last
+// word's positions = 0 mod 2, 4, 8; if all are 0, the sign bit of position 0's F value (-0 too).
+// Those are the partial sums the lane of position 0 sees in a butterfly at distance 8, 4, 2, 1 over
+// the last word, so the sign is carried as a mask m (0 / 0xFFFF per half): m' = (sum + m < 0), the
+// leaf's rep_level at 16 positions plus the accumulate step. About 20 VALU whatever n, where the
+// exact sign-magnitude chain over all n words took about 60 per word.
+// Bounds of the packed halves, per element BIAS +- |F| with |F| <= QMAG: an element with the
+// carried -1 stays positive; 16 of them do not carry into the other half of the 32-bit add;
+// sum + m - K * BIAS and acc + T + m keep their sign in 16 bits. They hold at every LLR_BITS of
+// SIGMAG; the rule is that of the 16-position tree, PAR 16. Elsewhere (CA2, PAR words of several
+// device words), and with -DPOLAR_REP_FALLBACK, POLAR_REP_CARRY is 0 and a zero total takes the
+// exact chain.
+// Emitted with the generated source, not in polar_sc_device.h: the pair kernels do not use it and
+// keep their code objects.
+const char *const kRepCarrySrc =
+    "#define POLAR_REP_QMAG_ ((1 << (POLAR_Q - 1)) - 1)\n"
+    "#define POLAR_REP_SAT_ ((1 << (POLAR_Q + POLAR_LPAR - 1)) - 1)\n"
+    "#if !defined(POLAR_REP_FALLBACK) && !POLAR_CA2 && POLAR_LPAR == 4 && 0x200 > POLAR_REP_QMAG_ + 1 && \\\n"
+    "    16 * (0x200 + POLAR_REP_QMAG_) < 0x10000 && POLAR_REP_SAT_ + 16 * POLAR_REP_QMAG_ + 1 < 0x8000\n"
+    "#define POLAR_REP_CARRY 1\n"
+    "static_assert(!CA2 && QMAG == POLAR_REP_QMAG_ && REPSAT == POLAR_REP_SAT_, \"REP carry bounds\");\n"
+    "template <int H, int K>\n"
+    "__device__ __forceinline__ void rep_carry_level(u32 &v, u32 &m)\n"
+    "{\n"
+    "    v += xorlane<H>(v);\n"
+    "    m = pk_sra(pk_sub(pk_add(v, m), (0x200u << K) * 0x00010001u), 15);\n"
+    "}\n"
+    "#else\n"
+    "#define POLAR_REP_CARRY 0\n"
+    "#endif\n";
+
 struct Gen {
     const std::vector<polar_sc_op> &ops;   // schedule of the code (or subtree) of 16 * 2^LG LLRs
     std::ostringstream o;
@@ -365,7 +401,7 @@ struct Gen {
             break;
         }
         case POLAR_OP_REP: {
-            // value chain in two's complement; the exact SM chain only when a total is 0
+            // value chain in two's complement; when a total is 0, the sign of zero from the last word
             o << "#ifndef REP_FSB\n#ifndef POLAR_REP_FSB\n"
                  "#define REP_FSB(I, a, b, fs) pk_mad_u16(pk_min(a, b), plane_pm1<I>(fs), 0x02000200u)\n"
                  "#else\n#define REP_FSB(I, a, b, fs) F_split_biased<I>(a, b, fs)\n#endif\n#endif\n";
@@ -388,12 +424,25 @@ struct Gen {
                 }
                 chunk_fence(i, n);
             }
+            // some frame of the wave has a zero total: the sign of zero from the last word alone,
+            // carried through its butterfly (kRepCarrySrc); a total that is not 0 keeps its sign
+            // under the carried 0 / -1. (-DPOLAR_REP_FALLBACK, and where the halves do not hold the
+            // bounds: the exact SM chain over all n words)
+            {
+                const std::string k = std::to_string((n - 1) / 16), I = std::to_string((n - 1) % 16);
+                o << "#if POLAR_REP_CARRY\n    if (rep_any_zero(acc_)) {\n"
+                  << "      u32 v_ = REP_FSB(" << I << ", " << M(sd, n - 1) << ", " << M(sd, 2 * n - 1) << ", FS_[" << k
+                  << "]), m_ = plane_mask<" << I << ">(FS_[" << k << "]);\n"
+                  << "      rep_carry_level<8, 1>(v_, m_); rep_carry_level<4, 2>(v_, m_); rep_carry_level<2, 3>(v_, m_); "
+                     "rep_carry_level<1, 4>(v_, m_);\n"
+                  << "      acc_ = row_bcast<lane_of_pos(0u)>(pk_add(acc_, m_));\n    }\n#else\n";
+            }
             o << "    if (rep_any_zero(acc_)) {\n      acc_ = 0u;\n";
             for (int i = 0; i < n; i++)
                 o << "      acc_ = G_sm<REPSAT>(row_add_tree(F_split_sm<" << i % 16 << ">(" << M(sd, i) << ", " << M(sd, n + i)
                   << ", FS_[" << i / 16 << "]), ln), acc_, 0u);\n";
             // two's complement or SM16: the hard decision is bit 15 / 31 either way
-            o << "    }\n    full_ = pk_sra(acc_, 15);\n";
+            o << "    }\n#endif\n    full_ = pk_sra(acc_, 15);\n";
             for (int j = 0; j < n; j += 16) put_mask(op.pos + j, n < 16 ? n : 16, "full_");
             o << "  }\n";
             clobber_parent(sd, n);
@@ -560,6 +609,7 @@ struct Gen {
         o << "#define POLAR_LANE_REMAP 1\n#define POLAR_Q " << p.cfg.llr_bits << "\n"
           << (p.cfg.extended ? "" : "#define POLAR_EXT 0\n")   // EXTENDED = 0: saturating leaves
           << "#include \"polar_sc_device.h\"\nusing namespace polar;\n"
+          << kRepCarrySrc
           << "typedef const __attribute__((address_space(1))) void *gas_t;\n"
           << "typedef __attribute__((address_space(3))) void *las_t;\n"
           << "extern \"C\" __global__ void __launch_bounds__(" << 64 * wpb << ", " << MASK_MIN_WAVES
@@ -701,7 +751,7 @@ std::string hybrid_source(const polar_sc_plan &p, bool with_subs = true, bool ch
       << (p.cfg.extended ? 1 : 0) << "\n#define POLAR_LPAR " << lpar << "\n#define POLAR_CHAN16 " << (chan16 ? 1 : 0)
       << "\n#include \"polar_sc_interp.h\"\n";
     if (with_subs) {
-        o << "namespace polar {\n#define CH(w) ch_load(cin_[(w) * 64])\n";
+        o << "namespace polar {\n" << kRepCarrySrc << "#define CH(w) ch_load(cin_[(w) * 64])\n";
         int lg = 0;
         while ((1 << lg) < p.sub_words) lg++;
         for (size_t id = 0; id < p.subs.size(); id++) {
