@@ -364,7 +364,7 @@ def all_items():
     # generated kernels (one code object per mask and configuration); the interpreter formats
     # share one per format
     items += sweep_items() + ca2_items() + q9_items() + par48_gpu_items() + high_rate_items() + issue_form_items()
-    items += leaf_block_items()
+    items += leaf_block_items() + spc_packed_items()
     return items
 
 
@@ -407,6 +407,27 @@ def leaf_block_items():
 
 def issue_form_items():
     return [("wide_spc4096", wide_spc_mask(), None, {"kernel": 2, "sub_words": 128})]
+
+
+# ---- the packed SPC epilogue, the multiply-add G+leaf entry and the packed root of the per-mask
+# kernel at the smallest codes that have them (tests/test_spc_packed_gpu.py). One 16-bit pattern
+# per 16-LLR word, position 0 in bit 0; 0xFFFE.. is an SPC node, 0xFFFF.. an R1 node. An SPC node
+# is a right child below the root's children, so one of 4 words needs N = 256 ----------------------
+SPC_PACKED_WORDS = {
+    "spc_n32": (0xE880, 0xFFFE),
+    "spc_n64": (0xE880, 0xFFFE, 0xFEE8, 0xFFFF),
+    "spc_n128": (0xE880, 0xFFFE, 0xFFFE, 0xFFFF, 0xE800, 0xFEE8, 0xFFFF, 0xFFFF),
+    "spc_n256": (0x0000, 0xE880, 0xFEE8, 0xFFFE, 0xFFFE, 0xFFFF, 0xFFFF, 0xFFFF,
+                 0xE880, 0xFEE8, 0xFFFE, 0xFFFF, 0xFFFF, 0xFFFF, 0xFFFF, 0xFFFF),
+}
+
+
+def spc_packed_mask(name):
+    return np.array([(w >> i) & 1 for w in SPC_PACKED_WORDS[name] for i in range(16)], np.uint8)
+
+
+def spc_packed_items():
+    return [(name, spc_packed_mask(name), None, None) for name in SPC_PACKED_WORDS]
 
 
 def prewarm_all(verbose=False):

@@ -95,6 +95,72 @@ const char *const kRepCarrySrc =
     "#define POLAR_REP_CARRY 0\n"
     "#endif\n";
 
+// Forms of the per-mask kernel alone (Gen::forms), emitted with its source as kRepCarrySrc is: the
+// pair and hybrid kernels do not use them and keep their code objects. Each has a switch back to
+// the former form (POLAR_SC_CLANG_FLAGS, for A/Bs); with all of them the kernel is the former one.
+//   * SPC nodes of <= 16 words whose keys (|lambda| << 10 | word << 4 | bitrev4(position)) stay
+//     below 0x8000: both frames stay in the halves of one register to the end. One packed min
+//     butterfly; the lane that flips is the one whose own key is the row minimum, a mask from the
+//     sign of min - own (<= 0, and above -0x8000 by the bound); the parity stays a bit per half and
+//     the flip is mask & parity moved to the word's bit by one packed shift. No compare, no select.
+//     POLAR_SPC_PACKED(n) is the bound; elsewhere the 32-bit epilogue. (-DPOLAR_SPC_EPILOGUE32)
+//   * row_transpose16_x: a stage of the 16 x 16 bit transpose is (x & M) | ((y << s) & ~M) on the
+//     lower lane and ((y >> s) & M) | (x & ~M) on the upper, y the partner's word. The bits a
+//     rotate by s wraps round fall under the side of the mask that takes x, so a stage is
+//     bfi(A, x, rotr(y, r)) with per-lane A = M / ~M and r = 32 - s / s: 3 VALU for 6.
+//     (-DPOLAR_OUT_TRANSPOSE6)
+// -DPOLAR_REP_FALLBACK stands for the kernel of before the REP carry as a whole (tests/test_rep_carry.py
+// pins its code object), so it takes the former forms of this list with it.
+const char *const kMaskFormsSrc =
+    "#ifdef POLAR_REP_FALLBACK\n"
+    "#define POLAR_SPC_EPILOGUE32\n#define POLAR_OUT_TRANSPOSE6\n"
+    "#endif\n"
+    "#define POLAR_SPC_GSAT_ ((1 << (POLAR_Q - 2)) - 1)\n"
+    "#if !defined(POLAR_SPC_EPILOGUE32) && !defined(POLAR_SPC_KEY32) && !POLAR_CA2\n"
+    "#define POLAR_SPC_PACKED(n) ((n) <= 16 && ((POLAR_SPC_GSAT_ << 10) | (((n) - 1) << 4) | 15) < 0x8000)\n"
+    "static_assert(!CA2 && GSAT == POLAR_SPC_GSAT_, \"SPC packed key bound\");\n"
+    "__device__ __forceinline__ u32 pk_shlv(u32 a, u32 s) { return U(V(a) << V(s)); }\n"
+    "__device__ __forceinline__ u32 row_pk_min(u32 v)\n"
+    "{\n"
+    "    v = pk_min(v, xorlane<8>(v));\n"
+    "    v = pk_min(v, xorlane<4>(v));\n"
+    "    v = pk_min(v, xorlane<2>(v));\n"
+    "    v = pk_min(v, xorlane<1>(v));\n"
+    "    return v;\n"
+    "}\n"
+    "#else\n"
+    "#define POLAR_SPC_PACKED(n) 0\n"
+    "#endif\n"
+    "#ifndef POLAR_OUT_TRANSPOSE6\n"
+    "struct OutT {\n"
+    "    u32 A8, A4, A2, A1, r8, r4, r2, r1;\n"
+    "    __device__ __forceinline__ void init(u32 pl)\n"
+    "    {\n"
+    "        // (the lane masks opaque: as a known 0 / -1 the optimiser turns mask ^ constant into a select on VCC)\n"
+    "        A8 = opaque(clear_mask<3>(pl)) ^ 0xFF00FF00u; r8 = ((pl & 8u) << 1) + 24u;   // (the rotate count is read mod 32)\n"
+    "        A4 = opaque(clear_mask<2>(pl)) ^ 0xF0F0F0F0u; r4 = ((pl & 4u) << 1) + 28u;\n"
+    "        A2 = opaque(clear_mask<1>(pl)) ^ 0xCCCCCCCCu; r2 = ((pl & 2u) << 1) + 30u;\n"
+    "        A1 = opaque(clear_mask<0>(pl)) ^ 0xAAAAAAAAu; r1 = ((pl & 1u) << 1) + 31u;\n"
+    "    }\n"
+    "};\n"
+    "template <int H>\n"
+    "__device__ __forceinline__ u32 transpose_stage(u32 v, u32 A, u32 r)\n"
+    "{\n"
+    "    const u32 p = xorlane_phys<H>(v);\n"
+    "    u32 d;   // (v_bfi_b32 named: the optimiser otherwise keeps ~A in a register for an AND-OR)\n"
+    "    asm(\"v_bfi_b32 %0, %1, %2, %3\" : \"=v\"(d) : \"v\"(A), \"v\"(v), \"v\"(__builtin_amdgcn_alignbit(p, p, r)));\n"
+    "    return d;\n"
+    "}\n"
+    "__device__ __forceinline__ u32 row_transpose16_x(u32 v, const OutT &t)\n"
+    "{\n"
+    "    v = transpose_stage<8>(v, t.A8, t.r8);\n"
+    "    v = transpose_stage<4>(v, t.A4, t.r4);\n"
+    "    v = transpose_stage<2>(v, t.A2, t.r2);\n"
+    "    v = transpose_stage<1>(v, t.A1, t.r1);\n"
+    "    return v;\n"
+    "}\n"
+    "#endif\n";
+
 struct Gen {
     const std::vector<polar_sc_op> &ops;   // schedule of the code (or subtree) of 16 * 2^LG LLRs
     std::ostringstream o;
@@ -107,6 +173,8 @@ struct Gen {
     // F / G word. C2: 158 -> 126 VGPRs, 3 -> 4 waves per SIMD, 76.7 -> 72.7 / 75.5 us on one
     // box
     bool pack = false;
+    // per-mask kernels: the forms of kMaskFormsSrc
+    bool forms = false;
     Gen(const std::vector<polar_sc_op> &ops_, int lg) : ops(ops_), LG(lg) {}
 
     // Partial sums: u32 bw[max(1, G / 16)], dword j = groups 16 j .. 16 j + 15, low frame in
@@ -481,6 +549,40 @@ struct Gen {
                 if (spc) o << "      par_ ^= h_; }\n";
                 else o << "    }\n";
             }
+            // per-mask kernels, nodes of <= 16 words with keys below 0x8000 (POLAR_SPC_PACKED,
+            // kMaskFormsSrc; a per-mask kernel has no wider SPC node: G <= 64 and a child of the root
+            // is never one): both frames stay packed. The lane's key is kk_ | br in both halves, the
+            // row minimum one packed butterfly; ne_ is all-ones in a half whose own key is not the
+            // minimum (keys differ in br, so exactly one lane of the row has it clear). The parity
+            // stays a bit per half: for one word it is the hard decision itself, already at the
+            // word's bit; for more words the population count of each half, bit 0 / 16, and the flip
+            // is moved to the word's bit (bits 4..7 of the minimum) by one packed shift. Same tie
+            // order: it is that of the key.
+            const bool packed = spc && forms && n <= 16;
+            if (packed) {
+                const int sh = op.pos % 16, j = op.pos / 16;
+                o << "#if POLAR_SPC_PACKED(" << n << ")\n"
+                  << "    static_assert(((GSAT << 10) | " << (((n - 1) << 4) | 15)
+                  << "u) < 0x8000u, \"SPC keys: minimum - own key keeps its sign in a 16-bit half\");\n";
+                if (n == 1) {
+                    o << "    par_ = row_xor(par_" << (sh ? " << " + std::to_string(sh) : std::string()) << ");\n";
+                } else {
+                    if (n < 16) {
+                        const unsigned m = (1u << n) - 1u;
+                        o << "    par_ &= 0x" << std::hex << (m | (m << 16)) << std::dec << "u;\n";
+                    }
+                    o << "    par_ = row_xor((u32)__builtin_popcount(par_ & 0xFFFFu) | ((u32)__builtin_popcount(par_ >> 16) << 16));\n";
+                }
+                o << "    const u32 k0_ = kk_ | ln.br | (ln.br << 16);\n"
+                  << "    const u32 km_ = row_pk_min(k0_);\n"
+                  << "    const u32 ne_ = opaque(pk_sra(pk_sub(km_, k0_), 15));\n";
+                if (n == 1)
+                    o << "    bw[" << j << "] ^= par_ & ~ne_ & " << hexmask(op.pos, 1) << ";\n";
+                else
+                    o << "    bw[" << j << "] ^= pk_shlv(par_ & ~ne_ & 0x00010001u, (km_ >> 4) & 0x000F000Fu)"
+                      << (sh ? " << " + std::to_string(sh) : std::string()) << ";\n";
+                o << "#else\n";
+            }
             if (spc) {
                 // parity of each frame's hard decisions; flip the partial sum at the least
                 // reliable position when it is odd
@@ -527,6 +629,7 @@ struct Gen {
                 }
                 o << "#endif\n";
             }
+            if (packed) o << "#endif\n";
             o << "  }\n";
             break;
         }
@@ -606,10 +709,11 @@ struct Gen {
         const int wpb = MASK_WPB;
         presplit = true;
         pack = G >= 2;
+        forms = true;
         o << "#define POLAR_LANE_REMAP 1\n#define POLAR_Q " << p.cfg.llr_bits << "\n"
           << (p.cfg.extended ? "" : "#define POLAR_EXT 0\n")   // EXTENDED = 0: saturating leaves
           << "#include \"polar_sc_device.h\"\nusing namespace polar;\n"
-          << kRepCarrySrc
+          << kRepCarrySrc << kMaskFormsSrc
           << "typedef const __attribute__((address_space(1))) void *gas_t;\n"
           << "typedef __attribute__((address_space(3))) void *las_t;\n"
           << "extern \"C\" __global__ void __launch_bounds__(" << 64 * wpb << ", " << MASK_MIN_WAVES
@@ -705,6 +809,15 @@ struct Gen {
         // or G rounded up to 4, polar_sc_host.cpp). The store predicates compare the row with the
         // number of frames the batch has left for this wave. (-DPOLAR_MASK_ADDR64: a 64-bit
         // pointer and frame index per lane)
+        // (the marker of tools/pair_census.py for the code after the last op)
+        o << "  // END: output transpose and stores\n";
+        // the transpose constants from the lane index, here: the stage arrays are dead, and taken
+        // from an opaque copy they are not live across the decode
+        o << "#ifndef POLAR_OUT_TRANSPOSE6\n"
+          << "  __builtin_amdgcn_sched_barrier(0);\n"
+          << "  u32 tl_ = ln.pl;\n  asm volatile(\"\" : \"+v\"(tl_));\n  OutT ot_; ot_.init(tl_);\n"
+          << "#define POLAR_TRANSPOSE16(v) row_transpose16_x(v, ot_)\n"
+          << "#else\n#define POLAR_TRANSPOSE16(v) row_transpose16(v, ln)\n#endif\n";
         o << "#ifndef POLAR_MASK_ADDR64\n"
           << "  const u32 nf_ = (u32)batch - wave * 8u;\n"
           << "  const bool st_lo = (u32)row < nf_, st_hi = (u32)row + 4u < nf_;\n"
@@ -720,7 +833,7 @@ struct Gen {
           << "#define POLAR_OUT(o, w) o[w]\n#define POLAR_OUTV(o, w) o[w]\n"
           << "#endif\n";
         for (int c = 0; c < (G + 15) / 16; c++) {
-            o << "  { const u32 t_ = row_transpose16(to_position_order(" << get16(16 * c) << ", ln), ln);\n"
+            o << "  { const u32 t_ = POLAR_TRANSPOSE16(to_position_order(" << get16(16 * c) << ", ln));\n"
               << "    if (" << 16 * c << " + pl < " << G << ") { if (st_lo) POLAR_OUT(o_lo, " << 16 * c
               << ") = (unsigned short)(t_ & 0xFFFFu); if (st_hi) POLAR_OUT(o_hi, " << 16 * c
               << ") = (unsigned short)(t_ >> 16); } }\n";

@@ -97,8 +97,11 @@ def form_cost(line):
 def drop_rep_fallback(src):
     """the generated source without the exact REP chains (taken only when a REP total is 0): the
     test and the branch stay (the asm comment keeps the emptied body from becoming a select)"""
-    return re.sub(r"(    if \(rep_any_zero\(acc_\)\) \{\n      acc_ = 0u;\n)(?:      acc_ = G_sm<REPSAT>.*\n)+",
-                  r'\1      asm volatile("; exact REP chain left out");\n', src)
+    src = re.sub(r"(    if \(rep_any_zero\(acc_\)\) \{\n      acc_ = 0u;\n)(?:      acc_ = G_sm<REPSAT>.*\n)+",
+                 r'\1      asm volatile("; exact REP chain left out");\n', src)
+    # the carried butterfly over the last word (POLAR_REP_CARRY), taken on the same condition
+    return re.sub(r"(#if POLAR_REP_CARRY\n    if \(rep_any_zero\(acc_\)\) \{\n)(?:      .*\n)+?(    \}\n#else\n)",
+                  r'\1      asm volatile("; REP carry left out");\n\2', src)
 
 
 def drop_unaligned_copy(src):
@@ -191,7 +194,10 @@ def mark_mask_kernel(src):
         if "polar_sc_mask_kernel(" in line:
             inside = True
         m = re.match(r"^  \{ // (\S+)(?: level \d+)? n (\d+)", line) or re.match(r"^  \{ // ([FG]\+leaf)", line)
-        if inside and m:
+        if inside and line.startswith("  // END:"):   # the code after the last op: a class of its own
+            out.append('  asm volatile(";@@ output"); __builtin_amdgcn_sched_barrier(0);')
+            n += 1
+        elif inside and m:
             if "leaf" in m.group(1):
                 label = "leaf"
             else:
