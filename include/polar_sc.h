@@ -278,6 +278,35 @@ int polar_load_mask_file(const char *path, uint8_t *mask_out, uint32_t cap, uint
 int polar_codeword_to_info(const polar_sc_plan *plan, const uint64_t *xhat, uint8_t *info_out,
                            size_t batch);
 
+/* Host-side inverse of polar_codeword_to_info: x = u . F^{(x)n} with the information positions of
+ * u taken from info ([batch][K] bytes, bit 0 of each) and the frozen ones zero.
+ * x: [batch][ceil(N/64)] uint64 host array (padding bits zero). */
+int polar_info_to_codeword(const polar_sc_plan *plan, const uint8_t *info, uint64_t *x, size_t batch);
+
+/* ---- Information bits on the device ----
+ * Information words: [batch][ceil(K/64)] uint64, bit k of a row = the k-th information bit in
+ * natural position order (the order of polar_codeword_to_info), bits >= K zero. Codeword rows
+ * are the x^ format of polar_sc_decode. All three calls are asynchronous on `stream` and run
+ * hipcc-built kernels on bit-packed rows (no generated code). The first call on a device
+ * uploads the plan's mask table (synchronously); polar_sc_plan_prepare uploads it too, after
+ * which the calls allocate nothing and may be captured into a graph (the library records
+ * kernels only, no memset node). batch <= 2^31 - 8; batch == 0 returns 0. */
+
+/* u^ = x^ . F^{(x)n} restricted to the information positions, packed. Every word of info_dev
+ * is written (the buffer may hold anything). K == 0: nothing to write, returns 0. */
+int polar_sc_extract_info(const polar_sc_plan *plan, const uint64_t *xhat_dev, uint64_t *info_dev, size_t batch,
+                          void *stream);
+
+/* The inverse: information words -> codeword rows x = u . F^{(x)n} (frozen bits zero). Bits of
+ * info_dev at and above K are ignored; every word of x_dev is written (N = 32: high half zero). */
+int polar_sc_encode(const polar_sc_plan *plan, const uint64_t *info_dev, uint64_t *x_dev, size_t batch,
+                    void *stream);
+
+/* polar_sc_decode into the caller's xhat_dev, then polar_sc_extract_info of it into info_dev,
+ * on the same stream. The library allocates nothing hidden for the pair. */
+int polar_sc_decode_info(const polar_sc_plan *plan, const int8_t *llr_dev, uint64_t *xhat_dev, uint64_t *info_dev,
+                         size_t batch, void *stream);
+
 int polar_sc_plan_get_stats(const polar_sc_plan *plan, polar_sc_plan_stats *stats);
 
 /* Copy the compiled schedule (at most cap ops) and its length. */

@@ -114,6 +114,7 @@ EXPORTS = (
     "polar_csim_frames", "polar_csim_states", "polar_count_errors",
     "polar_mask_from_order", "polar_write_frozen_tab", "polar_write_parameters_h", "polar_parse_parameters_h",
     "polar_sc_trace", "polar_sc_decode_i16", "polar_sc_debug_subtree", "polar_sc_plan_launch_info",
+    "polar_sc_extract_info", "polar_sc_encode", "polar_sc_decode_info", "polar_info_to_codeword",
 )
 
 _lib = None
@@ -149,6 +150,10 @@ def lib():
         "polar_load_frozen_tab": [ctypes.c_char_p, u32, u32, p, u32, ctypes.POINTER(u32)],
         "polar_load_mask_file": [ctypes.c_char_p, p, u32, ctypes.POINTER(u32)],
         "polar_codeword_to_info": [p, p, p, sz],
+        "polar_info_to_codeword": [p, p, p, sz],
+        "polar_sc_extract_info": [p, p, p, sz, p],
+        "polar_sc_encode": [p, p, p, sz, p],
+        "polar_sc_decode_info": [p, p, p, p, sz, p],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
         "polar_sc_selftest_lanes": [p],
@@ -317,6 +322,7 @@ class Decoder:
         self.N = int(mask.size)
         self.K = int(mask.sum())
         self.words = (self.N + 63) // 64
+        self.info_words = (self.K + 63) // 64
         return self
 
     def close(self):
@@ -496,6 +502,71 @@ class Decoder:
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(xhat)).view(np.uint64))
         out = np.zeros((x.shape[0], self.K), dtype=np.uint8)
         _check("polar_codeword_to_info", lib().polar_codeword_to_info(self._plan, _np_ptr(x), _np_ptr(out), x.shape[0]))
+        return out
+
+    def info_to_codeword(self, info):
+        """information bits [B, K] 0/1 (host) -> codeword words [B, ceil(N/64)] uint64 (x = u F^(x)n,
+        frozen bits zero): the inverse of codeword_to_info."""
+        u = np.ascontiguousarray(np.atleast_2d(np.asarray(info)), dtype=np.uint8)
+        if u.shape[1] != self.K:
+            raise ValueError("info must be [B, %d]" % self.K)
+        out = np.zeros((u.shape[0], self.words), dtype=np.uint64)
+        _check("polar_info_to_codeword", lib().polar_info_to_codeword(self._plan, _np_ptr(u), _np_ptr(out), u.shape[0]))
+        return out
+
+    # -- information bits on the device (DESIGN.md 3.8) ----------------------------------------
+    def _xform(self, fn, src, cols_in, cols_out, out, stream, name):
+        torch = _torch()
+        if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.int64):
+            raise TypeError("%s must be a CUDA int64 tensor" % name)
+        if src.dim() != 2 or src.shape[1] != cols_in or not src.is_contiguous():
+            raise ValueError("%s must be contiguous [B, %d]" % (name, cols_in))
+        B = src.shape[0]
+        if out is None:
+            out = torch.empty((B, cols_out), dtype=torch.int64, device=src.device)
+        else:
+            self._check_out(out, src, (B, cols_out), torch.int64)
+        if out.numel() == 0:     # K == 0: nothing to extract, no launch
+            return out
+        with torch.cuda.device(src.device):
+            s = stream if stream is not None else torch.cuda.current_stream(src.device)
+            _check(fn, getattr(lib(), fn)(self._plan, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(out.data_ptr()), B,
+                                          ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    def extract_info(self, xhat, out=None, stream=None):
+        """x^ words (torch.int64 CUDA [B, ceil(N/64)], as decode() returns) -> information words
+        [B, info_words]: bit k of a row = the k-th information bit (the order of
+        codeword_to_info), bits >= K zero; unpack_bits(out, K) gives the [B, K] bytes.
+        Asynchronous on `stream`."""
+        return self._xform("polar_sc_extract_info", xhat, self.words, self.info_words, out, stream, "xhat")
+
+    def encode(self, info, out=None, stream=None):
+        """The inverse: information words [B, info_words] -> codeword words [B, ceil(N/64)] (frozen
+        bits zero; bits of `info` at and above K are ignored)."""
+        return self._xform("polar_sc_encode", info, self.info_words, self.words, out, stream, "info")
+
+    def decode_info(self, llr, out=None, xhat=None, stream=None):
+        """decode() followed by extract_info() on the same stream: int8 LLRs [B, N] -> information
+        words [B, info_words]. `xhat` (optional, [B, ceil(N/64)]) receives the codeword estimate."""
+        torch = self._check_llr(llr)
+        B = llr.shape[0]
+        if xhat is None:
+            xhat = torch.empty((B, self.words), dtype=torch.int64, device=llr.device)
+        else:
+            self._check_out(xhat, llr, (B, self.words), torch.int64)
+        if out is None:
+            out = torch.empty((B, self.info_words), dtype=torch.int64, device=llr.device)
+        else:
+            self._check_out(out, llr, (B, self.info_words), torch.int64)
+        if self.K == 0:
+            self.decode(llr, xhat, stream)
+            return out
+        with torch.cuda.device(llr.device):
+            s = stream if stream is not None else torch.cuda.current_stream(llr.device)
+            _check("polar_sc_decode_info", lib().polar_sc_decode_info(
+                self._plan, ctypes.c_void_p(llr.data_ptr()), ctypes.c_void_p(xhat.data_ptr()),
+                ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(s.cuda_stream)))
         return out
 
 

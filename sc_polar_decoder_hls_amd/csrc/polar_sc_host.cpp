@@ -26,6 +26,12 @@ extern "C" int polar_sc_launch_decode(int gmem, const int8_t *llr, uint16_t *out
                                       int waves_per_group, int groups_per_block, int group_dwords,
                                       int lds_dwords, int lds0, void *stream, unsigned long long *trace);
 extern "C" int polar_sc_launch_selftest(uint32_t *out_dev);
+// polar_sc_xform.hip: the per-dword mask table (8 dwords per record) and the transform launches
+// (0, a hipError_t, or -1 for a batch beyond one grid)
+extern "C" void polar_sc_xform_table(const uint8_t *mask, uint32_t N, uint32_t *tab);
+extern "C" int polar_sc_launch_xform(int encode, const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev,
+                                     uint32_t N, uint32_t K, size_t batch, void *stream);
+extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stream);
 
 using polar_host::DevState;
 
@@ -650,6 +656,49 @@ int decode_common(const polar_sc_plan *p, const int8_t *llr, uint16_t *out, size
     return rc ? -EIO : 0;
 }
 
+// the transform kernels' mask table on the current device (built and uploaded once per device,
+// under the plan lock; nothing of the decode kernels is compiled or loaded for it)
+int ensure_xform(const polar_sc_plan *p, const void **tab)
+{
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return hip_fail("hipGetDevice", e);
+    std::lock_guard<std::mutex> lk(p->mu);
+    DevState &st = p->dev[dev];
+    if (!st.xtab) {
+        std::vector<uint32_t> tab8((size_t)(p->N / 32u) * 8u);
+        polar_sc_xform_table(p->mask.data(), p->N, tab8.data());
+        void *d = nullptr;
+        if (hipMalloc(&d, tab8.size() * 4u) != hipSuccess) return -ENOMEM;
+        if (hipError_t e = hipMemcpy(d, tab8.data(), tab8.size() * 4u, hipMemcpyHostToDevice); e != hipSuccess) {
+            (void)hipFree(d);
+            return hip_fail("transform table upload", e);
+        }
+        st.xtab = d;
+    }
+    *tab = st.xtab;
+    return 0;
+}
+
+// extraction (encode = 0: x^ rows -> information rows) / encoding (1: the reverse) of resident frames
+int xform_common(const polar_sc_plan *p, int encode, const uint64_t *in, uint64_t *out, size_t batch, void *stream)
+{
+    // (a K = 0 plan has empty information rows: that pointer may be anything)
+    if (!p || (batch > 0 && p->K > 0 && (!in || !out))) return -EINVAL;
+    if (batch == 0) return 0;
+    if (batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    if (p->K == 0 && encode && !out) return -EINVAL;
+    int rc = 0;
+    if (p->K == 0) {   // no information bit: nothing to extract; the codeword is all zero
+        rc = encode ? polar_sc_launch_xform_clear(out, batch * (size_t)((p->N + 63u) / 64u), stream) : 0;
+    } else {
+        const void *tab = nullptr;
+        if (const int e = ensure_xform(p, &tab)) return e;
+        rc = polar_sc_launch_xform(encode, tab, in, out, p->N, p->K, batch, stream);
+    }
+    if (rc < 0) return -EINVAL;
+    return rc ? hip_fail("transform launch", (hipError_t)rc) : 0;
+}
+
 // The per-op monitor (the analogue of the reference's sc_monitor latency report,
 // src/rtl_simu_testbench/sc_monitor/sc_monitor.h:50-140, fed by my_module's Fct_ID / N_value
 // ports, my_module.h:21-30): one decode with the traced interpreter (hybrid plans: the
@@ -1121,6 +1170,7 @@ int polar_sc_plan_destroy(polar_sc_plan *p)
         if (kv.second.ops16) (void)hipFree(kv.second.ops16);
         if (kv.second.scratch) (void)hipFree(kv.second.scratch);
         if (kv.second.wide) (void)hipFree(kv.second.wide);
+        if (kv.second.xtab) (void)hipFree(kv.second.xtab);
     }
     if (have_dev && !p->dev.empty()) (void)hipSetDevice(cur);
     delete p;
@@ -1134,8 +1184,31 @@ int polar_sc_plan_prepare(const polar_sc_plan *p, size_t max_batch)
     // automatic layout: only the plan that decodes max_batch frames (layout_for) gets its
     // schedule and scratch here; the other one is set up by the first decode that uses it
     // (a caller of large batches must not pay the solo scratch, ~0.6 GB at C5)
+    const polar_sc_plan *plan = p;
     if (p->alt) p = layout_for(p, max_batch ? max_batch : 1, current_simds());
-    return ensure_device(p, max_batch ? max_batch : 1, &st);
+    if (const int rc = ensure_device(p, max_batch ? max_batch : 1, &st)) return rc;
+    // the mask table of polar_sc_extract_info / polar_sc_encode / polar_sc_decode_info
+    const void *tab = nullptr;
+    return plan->K ? ensure_xform(plan, &tab) : 0;
+}
+
+int polar_sc_extract_info(const polar_sc_plan *p, const uint64_t *xhat_dev, uint64_t *info_dev, size_t batch,
+                          void *stream)
+{
+    return xform_common(p, 0, xhat_dev, info_dev, batch, stream);
+}
+
+int polar_sc_encode(const polar_sc_plan *p, const uint64_t *info_dev, uint64_t *x_dev, size_t batch, void *stream)
+{
+    return xform_common(p, 1, info_dev, x_dev, batch, stream);
+}
+
+int polar_sc_decode_info(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *xhat_dev, uint64_t *info_dev,
+                         size_t batch, void *stream)
+{
+    if (!p || (batch > 0 && (!llr_dev || !xhat_dev || (p->K > 0 && !info_dev)))) return -EINVAL;
+    if (const int rc = polar_sc_decode(p, llr_dev, xhat_dev, batch, stream)) return rc;
+    return xform_common(p, 0, xhat_dev, info_dev, batch, stream);
 }
 
 int polar_sc_decode(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *hard_bits_dev,
@@ -1295,6 +1368,26 @@ int polar_codeword_to_info(const polar_sc_plan *p, const uint64_t *xhat, uint8_t
         uint32_t k = 0;
         for (uint32_t i = 0; i < N; i++)
             if (p->mask[i]) o[k++] = v[i];
+    }
+    return 0;
+}
+
+int polar_info_to_codeword(const polar_sc_plan *p, const uint8_t *info, uint64_t *x, size_t batch)
+{
+    if (!p || (batch > 0 && (!x || (p->K > 0 && !info)))) return -EINVAL;
+    const uint32_t N = p->N;
+    const size_t words = (N + 63) / 64;
+    std::vector<uint8_t> v(N);
+    for (size_t f = 0; f < batch; f++) {
+        const uint8_t *u = info + f * p->K;
+        uint32_t k = 0;
+        for (uint32_t i = 0; i < N; i++) v[i] = p->mask[i] ? (uint8_t)(u[k++] & 1u) : (uint8_t)0;
+        for (uint32_t h = 1; h < N; h <<= 1)           // x = u F^{(x)n}
+            for (uint32_t b = 0; b < N; b += 2 * h)
+                for (uint32_t j = b; j < b + h; j++) v[j] ^= v[j + h];
+        uint64_t *o = x + f * words;
+        for (size_t w = 0; w < words; w++) o[w] = 0;
+        for (uint32_t i = 0; i < N; i++) o[i >> 6] |= (uint64_t)v[i] << (i & 63);
     }
     return 0;
 }

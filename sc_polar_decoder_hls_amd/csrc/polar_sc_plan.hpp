@@ -32,6 +32,7 @@ struct DevState {
     hipModule_t module16 = nullptr;     // interpreter on the int16 channel (polar_sc_decode_i16)
     hipFunction_t fn16 = nullptr;
     void *ops16 = nullptr;              //   and its schedule when it differs from `ops`
+    void *xtab = nullptr;               // per-dword mask table of the transform kernels (polar_sc_xform.hip)
     int simds = 0;                // SIMDs of the device (4 per CU), for launch sizing
     // registers per lane (VGPR + AGPR allocation, kernel descriptor) of the generated decode
     // kernel and of the pair segment kernel: the launch shape is capped so that a block's
