@@ -307,6 +307,48 @@ int polar_sc_encode(const polar_sc_plan *plan, const uint64_t *info_dev, uint64_
 int polar_sc_decode_info(const polar_sc_plan *plan, const int8_t *llr_dev, uint64_t *xhat_dev, uint64_t *info_dev,
                          size_t batch, void *stream);
 
+/* ---- Float channel values ----
+ * The reference's sc_quantizer (src/testbench/sc_quantizer/sc_quantizer.h:76-80) on the device:
+ * q = clamp((short)(v * beta), vsatn, vsatp). The value is widened to fp32 (exact for half and
+ * bfloat16), multiplied once by (float)beta (no contraction), converted as the reference's cast
+ * does on x86-64 (truncation toward zero; NaN and values outside the 32-bit range give 0; then the
+ * low 16 bits, so |v * beta| >= 32768 WRAPS, it does not saturate) and clamped.
+ * Everywhere: dtype one of the three below, 1 <= beta <= 255 (sc_uint<8>), vsatn <= vsatp and
+ * both inside the output type, pointers aligned to their element; -EINVAL otherwise. */
+enum { POLAR_SC_F32 = 0, POLAR_SC_F16 = 1, POLAR_SC_BF16 = 2 };
+
+/* n values at v_dev -> int8 (bits = 8) or int16 (bits = 16) at q_dev, for any data. One launch,
+ * nothing allocated; 16-byte aligned pointers take the vector path throughout, others a scalar
+ * head / tail or element loads. Asynchronous on `stream`. */
+int polar_sc_quantize(const void *v_dev, int dtype, size_t n, int beta, int vsatn, int vsatp,
+                      void *q_dev, int bits, void *stream);
+
+typedef struct polar_sc_soft_info {
+    uint32_t fused;            /* 1: the decode kernel quantizes while it stages the frames (per-mask
+                                  plans); 0: polar_sc_quantize into the workspace, then the decode */
+    uint32_t regs;             /* registers per lane of the fused kernel, else 0 */
+    uint64_t workspace_bytes;  /* bytes the caller must pass as workspace for `batch` frames: 0 when
+                                  fused, else batch * N (int8), or 2 * batch * N for LLR_BITS 9
+                                  (int16) */
+    uint64_t code_key;         /* as polar_sc_launch_info.code_key, of the fused kernel */
+} polar_sc_soft_info;
+
+/* Host only. Compiles the fused kernel of `dtype` if needed, as polar_sc_plan_launch_info does
+ * the plan's. */
+int polar_sc_soft_info_get(const polar_sc_plan *plan, int dtype, size_t batch, polar_sc_soft_info *info);
+
+/* polar_sc_decode of float channel values v_dev[batch][N]: hard_bits_dev receives what
+ * polar_sc_decode gives on the quantized frames (polar_sc_decode_i16 for LLR_BITS 9, whose
+ * bounds may use the int16 range; int8 otherwise).
+ *   workspace: at least workspace_bytes of polar_sc_soft_info_get, 16-byte aligned, contents
+ *   unspecified afterwards. May be NULL when workspace_bytes == 0.
+ * The first soft decode of a dtype on a device loads the fused kernel synchronously (and
+ * compiles it if no polar_sc_soft_info_get did); later calls allocate nothing and can be
+ * captured in a graph. Asynchronous on `stream`; batch == 0 returns 0. */
+int polar_sc_decode_soft(const polar_sc_plan *plan, const void *v_dev, int dtype, int beta,
+                         int vsatn, int vsatp, void *workspace, uint64_t *hard_bits_dev,
+                         size_t batch, void *stream);
+
 int polar_sc_plan_get_stats(const polar_sc_plan *plan, polar_sc_plan_stats *stats);
 
 /* Copy the compiled schedule (at most cap ops) and its length. */

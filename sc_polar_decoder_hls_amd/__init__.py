@@ -23,7 +23,7 @@ from . import _build
 __all__ = [
     "Decoder", "PolarError", "load_frozen_tab", "load_mask_file", "unpack_bits", "pack_bits",
     "default_config", "make_tuning", "lib", "selftest_lanes", "OPS", "build", "csim_sigma", "csim_states", "csim_frames",
-    "count_errors",
+    "count_errors", "quantize", "SOFT_DTYPES",
 ]
 
 build = _build.build
@@ -103,6 +103,15 @@ class polar_sc_launch_info(ctypes.Structure):
                 ("alt_max_batch", ctypes.c_uint64)]
 
 
+class polar_sc_soft_info(ctypes.Structure):
+    _fields_ = [("fused", ctypes.c_uint32), ("regs", ctypes.c_uint32), ("workspace_bytes", ctypes.c_uint64),
+                ("code_key", ctypes.c_uint64)]
+
+
+# POLAR_SC_F32 / F16 / BF16 by torch dtype name (float channel values, include/polar_sc.h)
+SOFT_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+
+
 # exported symbols of include/polar_sc.h (tests check that the library exports all of them)
 EXPORTS = (
     "polar_sc_default_config", "polar_sc_plan_create", "polar_sc_plan_create_tuned", "polar_sc_plan_destroy",
@@ -115,6 +124,7 @@ EXPORTS = (
     "polar_mask_from_order", "polar_write_frozen_tab", "polar_write_parameters_h", "polar_parse_parameters_h",
     "polar_sc_trace", "polar_sc_decode_i16", "polar_sc_debug_subtree", "polar_sc_plan_launch_info",
     "polar_sc_extract_info", "polar_sc_encode", "polar_sc_decode_info", "polar_info_to_codeword",
+    "polar_sc_quantize", "polar_sc_soft_info_get", "polar_sc_decode_soft",
 )
 
 _lib = None
@@ -154,6 +164,9 @@ def lib():
         "polar_sc_extract_info": [p, p, p, sz, p],
         "polar_sc_encode": [p, p, p, sz, p],
         "polar_sc_decode_info": [p, p, p, p, sz, p],
+        "polar_sc_quantize": [p, i32, sz, i32, i32, i32, p, i32, p],
+        "polar_sc_soft_info_get": [p, i32, sz, p],
+        "polar_sc_decode_soft": [p, p, i32, i32, i32, i32, p, p, sz, p],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
         "polar_sc_selftest_lanes": [p],
@@ -323,6 +336,7 @@ class Decoder:
         self.K = int(mask.sum())
         self.words = (self.N + 63) // 64
         self.info_words = (self.K + 63) // 64
+        self.llr_bits = int((config if config is not None else default_config()).llr_bits)
         return self
 
     def close(self):
@@ -514,6 +528,55 @@ class Decoder:
         _check("polar_info_to_codeword", lib().polar_info_to_codeword(self._plan, _np_ptr(u), _np_ptr(out), u.shape[0]))
         return out
 
+    # -- float channel values ---------------------------------------------------
+    def soft_info(self, dtype, batch):
+        """How decode_soft() of `batch` frames of `dtype` (a torch float dtype) runs, as a dict:
+        fused, regs, workspace_bytes, code_key (16 hex digits). Host only; compiles the fused
+        kernel if needed."""
+        r = polar_sc_soft_info()
+        _check("polar_sc_soft_info_get", lib().polar_sc_soft_info_get(self._plan, _soft_dtype(dtype), int(batch),
+                                                                      ctypes.byref(r)))
+        d = {f: getattr(r, f) for f, _ in polar_sc_soft_info._fields_}
+        d["code_key"] = "%016x" % r.code_key
+        return d
+
+    def decode_soft(self, v, beta=4, vsatn=None, vsatp=None, out=None, workspace=None, stream=None):
+        """decode() of float channel values: v a float32 / float16 / bfloat16 CUDA tensor [B, N]
+        (contiguous), quantized as the reference's sc_quantizer does, clamp((short)(v * beta), vsatn,
+        vsatp); the bounds default to +-(2^(llr_bits-1) - 1). Per-mask plans quantize inside the
+        decode kernel; others need a workspace of soft_info()["workspace_bytes"] bytes (a uint8
+        CUDA tensor, 16-byte aligned), allocated here when not given. Asynchronous on `stream`."""
+        torch = _torch()
+        if not (isinstance(v, torch.Tensor) and v.is_cuda):
+            raise TypeError("v must be a CUDA float32, float16 or bfloat16 tensor")
+        dt = _soft_dtype(v.dtype)
+        if v.dim() != 2 or v.shape[1] != self.N or not v.is_contiguous():
+            raise ValueError("v must be contiguous [B, %d]" % self.N)
+        B = v.shape[0]
+        lim = (1 << (self.llr_bits - 1)) - 1
+        vsatn = -lim if vsatn is None else int(vsatn)
+        vsatp = lim if vsatp is None else int(vsatp)
+        if out is None:
+            out = torch.empty((B, self.words), dtype=torch.int64, device=v.device)
+        else:
+            self._check_out(out, v, (B, self.words), torch.int64)
+        need = self.soft_info(v.dtype, B)["workspace_bytes"] if B else 0
+        if need and workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=v.device)
+        if workspace is not None:
+            if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous()
+                    and workspace.device == v.device):
+                raise ValueError("workspace must be a contiguous CUDA tensor on the device of v")
+            if workspace.numel() * workspace.element_size() < need:
+                raise ValueError("workspace must hold %d bytes" % need)
+        with torch.cuda.device(v.device):
+            s = stream if stream is not None else torch.cuda.current_stream(v.device)
+            _check("polar_sc_decode_soft", lib().polar_sc_decode_soft(
+                self._plan, ctypes.c_void_p(v.data_ptr()), dt, int(beta), vsatn, vsatp,
+                ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None,
+                ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(s.cuda_stream)))
+        return out
+
     # -- information bits on the device (DESIGN.md 3.8) ----------------------------------------
     def _xform(self, fn, src, cols_in, cols_out, out, stream, name):
         torch = _torch()
@@ -568,6 +631,37 @@ class Decoder:
                 self._plan, ctypes.c_void_p(llr.data_ptr()), ctypes.c_void_p(xhat.data_ptr()),
                 ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(s.cuda_stream)))
         return out
+
+
+def _soft_dtype(dtype):
+    """torch dtype (or its name, or the POLAR_SC_* code) of float channel values -> the code"""
+    if isinstance(dtype, int):
+        return dtype
+    name = str(dtype).replace("torch.", "")
+    if name not in SOFT_DTYPES:
+        raise TypeError("channel values must be float32, float16 or bfloat16, not %s" % dtype)
+    return SOFT_DTYPES[name]
+
+
+def quantize(v, beta=4, vsatn=-31, vsatp=31, bits=8, out=None, stream=None):
+    """The reference's sc_quantizer on the GPU, for any data: clamp((short)(v * beta), vsatn, vsatp)
+    of a contiguous float32 / float16 / bfloat16 CUDA tensor -> int8 (bits = 8) or int16 (bits =
+    16) tensor of the same shape (`out` when given). Asynchronous on `stream`."""
+    torch = _torch()
+    if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
+        raise TypeError("v must be a contiguous CUDA tensor")
+    dt = _soft_dtype(v.dtype)
+    qt = {8: torch.int8, 16: torch.int16}.get(bits)
+    if out is None:
+        out = torch.empty(v.shape, dtype=qt or torch.int8, device=v.device)
+    elif qt is not None:
+        Decoder._check_out(out, v, v.shape, qt)
+    with torch.cuda.device(v.device):
+        s = stream if stream is not None else torch.cuda.current_stream(v.device)
+        _check("polar_sc_quantize", lib().polar_sc_quantize(
+            ctypes.c_void_p(v.data_ptr()), dt, v.numel(), int(beta), int(vsatn), int(vsatp),
+            ctypes.c_void_p(out.data_ptr()), int(bits), ctypes.c_void_p(s.cuda_stream)))
+    return out
 
 
 def selftest_lanes():

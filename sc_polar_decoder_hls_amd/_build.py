@@ -14,12 +14,14 @@ LIB = os.path.join(PKG, "lib", "libpolar_sc.so")
 SOURCES = [os.path.join(PKG, "csrc", "polar_sc_kernels.hip"), os.path.join(PKG, "csrc", "polar_sc_host.cpp"),
            os.path.join(PKG, "csrc", "polar_sc_jit.cpp"), os.path.join(PKG, "csrc", "polar_sc_pairgen.cpp"),
            os.path.join(PKG, "csrc", "polar_sc_channel.hip"), os.path.join(PKG, "csrc", "polar_sc_xform.hip"),
-           os.path.join(PKG, "csrc", "polar_sc_tables.cpp")]
+           os.path.join(PKG, "csrc", "polar_sc_soft.hip"), os.path.join(PKG, "csrc", "polar_sc_tables.cpp")]
+SOFT_SRC = os.path.join(PKG, "csrc", "polar_sc_soft.hip")
 DEVICE_H = os.path.join(PKG, "csrc", "polar_sc_device.h")
 INTERP_H = os.path.join(PKG, "csrc", "polar_sc_interp.h")
 PAIR_H = os.path.join(PKG, "csrc", "polar_sc_pair.h")
+QUANT_H = os.path.join(PKG, "csrc", "polar_sc_quant.h")
 HEADERS = [os.path.join(ROOT, "include", "polar_sc.h"), DEVICE_H, INTERP_H, PAIR_H, os.path.join(PKG, "csrc", "polar_sc_plan.hpp"),
-           os.path.join(PKG, "csrc", "polar_sc_glibcf.h")]
+           os.path.join(PKG, "csrc", "polar_sc_glibcf.h"), QUANT_H]
 GEN_DIR = os.path.join(PKG, "build")
 CLI_SRC = os.path.join(ROOT, "examples", "polar_decode_cli.c")
 CLI = os.path.join(PKG, "lib", "polar_decode_cli")
@@ -70,7 +72,8 @@ def build(force=False, verbose=False):
     # embed the device headers for hipRTC (per-mask kernels are compiled at plan time)
     for path, inc, name in ((DEVICE_H, "polar_sc_device_src.inc", "kPolarDeviceSrc"),
                             (INTERP_H, "polar_sc_interp_src.inc", "kPolarInterpSrc"),
-                            (PAIR_H, "polar_sc_pair_src.inc", "kPolarPairSrc")):
+                            (PAIR_H, "polar_sc_pair_src.inc", "kPolarPairSrc"),
+                            (QUANT_H, "polar_sc_quant_src.inc", "kPolarQuantSrc")):
         with open(path) as f:
             src = strip_comments(f.read())
         assert ")POLARSRC\"" not in src
@@ -88,12 +91,23 @@ def build(force=False, verbose=False):
     except (OSError, subprocess.SubprocessError):
         ver = "unknown"
     ver = "".join(ch for ch in ver if ch.isalnum() or ch in " .-_()/+:")
-    cmd = [hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
-           '-DPOLAR_ROCM_CLANG="%s"' % clang, '-DPOLAR_ROCM_CLANG_VERSION="%s"' % ver,
-           "-I" + os.path.join(ROOT, "include"), "-I" + GEN_DIR] + SOURCES + ["-o", tmp, "-lhiprtc", "-lz"]
+    common = [hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall",
+              "-I" + os.path.join(ROOT, "include"), "-I" + GEN_DIR]
+    # the float front end (polar_sc_soft.hip) on its own, without packed fp32 instructions: an
+    # object of its own, so that every other source keeps the flags it was built with before
+    soft_obj = os.path.join(GEN_DIR, "polar_sc_soft.%d.o" % os.getpid())
+    cmd = common + ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-c", SOFT_SRC, "-o", soft_obj]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
+    cmd = common + ["-shared", '-DPOLAR_ROCM_CLANG="%s"' % clang, '-DPOLAR_ROCM_CLANG_VERSION="%s"' % ver] + \
+        [s for s in SOURCES if s != SOFT_SRC] + ["-Wl," + soft_obj, "-o", tmp, "-lhiprtc", "-lz"]   # (-Wl: not a HIP source)
+    if verbose:
+        print(" ".join(cmd))
+    try:
+        subprocess.check_call(cmd)
+    finally:
+        os.remove(soft_obj)
     os.replace(tmp, LIB)
     return LIB
 
@@ -111,7 +125,7 @@ def _compile_item(item):
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     import sc_polar_decoder_hls_amd as pkg
-    name, m, cfg, tun = item
+    name, m, cfg, tun = item[:4]
     t0 = time.time()
     c = None
     if cfg is not None:
@@ -120,6 +134,8 @@ def _compile_item(item):
             setattr(c, k, v)
     dec = pkg.Decoder(m, c, tuning=tun)
     ok = dec.compile()
+    for dt in item[4] if len(item) > 4 else ():   # the fused kernels of decode_soft (_plansets.soft_items)
+        dec.soft_info(dt, 8)
     dec.close()
     return name, tun, ok, time.time() - t0
 
@@ -195,5 +211,6 @@ def _default_procs():
 
 def prewarm_items(items, procs=None, verbose=False):
     """Compile the hipRTC kernels of [(name, info mask, config fields dict or None, tuning dict
-    or None)] into the code-object cache (host only, in parallel)."""
+    or None[, input types whose decode_soft kernels to build too])] into the code-object cache
+    (host only, in parallel)."""
     _run_pool(list(items), procs or _default_procs(), verbose)

@@ -430,6 +430,24 @@ def spc_packed_items():
     return [(name, spc_packed_mask(name), None, None) for name in SPC_PACKED_WORDS]
 
 
+# ---- float channel values (tests/test_soft.py, tests/test_soft_gpu.py): the plans whose fused
+# kernels (one per input type, Decoder.soft_info) the tests decode with, and the plans of the
+# two-launch path --------------------------------------------------------------------------------
+SOFT_DTYPES = ("float32", "float16", "bfloat16")
+SOFT_FUSED_MASKS = ("spc_n32", "FB_N128_K64", "FB_N256_K128", "FB_N1024_K512")
+
+
+def soft_mask(name):
+    return spc_packed_mask(name) if name in SPC_PACKED_WORDS else mask(name)
+
+
+def soft_items():
+    """(name, mask, config fields, tuning, input types of the fused kernels to build)"""
+    return [(n, soft_mask(n), None, None, SOFT_DTYPES) for n in SOFT_FUSED_MASKS] + \
+        [("FB_N128_K64", mask("FB_N128_K64"), {"llr_bits": 8}, None, ("float32",)),
+         ("frozen_n_2048_k_1024", mask("frozen_n_2048_k_1024"), {"llr_bits": 9}, None, ())]
+
+
 def prewarm_all(verbose=False):
     """Compile every plan of all_items() into lib/rtc_cache/: each distinct plan once, all of
     them in one pool of worker processes (a clean build compiles ~650 kernels, hours of one
@@ -459,6 +477,7 @@ def prewarm_all(verbose=False):
         sources.add(h)
     _build.prewarm_items(first, verbose=verbose)
     _build.prewarm_items(second, verbose=verbose)
+    _build.prewarm_items(soft_items(), verbose=verbose)   # (after their int8 plans: the same masks)
 
 
 # ---- high-rate codes across the formats (tests/test_gpu_formats.py

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "polar_sc_glibcf.h"
+#include "polar_sc_quant.h"
 
 #include <cerrno>
 #include <cstring>
@@ -141,13 +142,7 @@ __device__ __forceinline__ uint32_t xs_next(uint32_t &x, uint32_t &y, uint32_t &
     return w;
 }
 
-// (short)(float) of the reference on x86-64: 32-bit truncating conversion (out of range ->
-// 0x80000000), then the low 16 bits
-__device__ __forceinline__ int to_short(float v)
-{
-    const int32_t i = (v > -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : (int32_t)0x80000000u;
-    return (int)(int16_t)(uint16_t)(uint32_t)i;
-}
+using polar_quant::to_short;   // (short)(float) of the reference (polar_sc_quant.h)
 
 __global__ void __launch_bounds__(256) csim_kernel(const uint32_t *__restrict__ states, const uint8_t *__restrict__ cw,
                                                   int ncw, uint64_t frame0, uint32_t N, long batch, float sigma,

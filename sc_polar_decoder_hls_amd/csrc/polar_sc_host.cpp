@@ -32,6 +32,9 @@ extern "C" void polar_sc_xform_table(const uint8_t *mask, uint32_t N, uint32_t *
 extern "C" int polar_sc_launch_xform(int encode, const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev,
                                      uint32_t N, uint32_t K, size_t batch, void *stream);
 extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stream);
+// polar_sc_soft.hip: the stand-alone quantizer (0 or a hipError_t; arguments checked here)
+extern "C" int polar_sc_launch_quantize(const void *v_dev, int dtype, size_t n, int beta, int vsatn, int vsatp,
+                                        void *q_dev, int bits, void *stream);
 
 using polar_host::DevState;
 
@@ -699,6 +702,30 @@ int xform_common(const polar_sc_plan *p, int encode, const uint64_t *in, uint64_
     return rc ? hip_fail("transform launch", (hipError_t)rc) : 0;
 }
 
+// ---- float channel values (include/polar_sc.h) -------------------------------
+// the quantizer's arguments: bounds inside the int8 / int16 output (bits = 8 / 16)
+bool quant_args_ok(int dtype, int beta, int vsatn, int vsatp, int bits)
+{
+    const int lim = bits == 16 ? 32768 : 128;
+    return dtype >= POLAR_SC_F32 && dtype <= POLAR_SC_BF16 && beta >= 1 && beta <= 255 && vsatn <= vsatp &&
+           vsatn >= -lim && vsatp < lim;
+}
+bool elem_aligned(const void *v, int dtype) { return ((uintptr_t)v & (dtype == POLAR_SC_F32 ? 3u : 1u)) == 0u; }
+// channel type of a plan's quantized frames: int16 for 9-bit LLRs (polar_sc_decode_i16), else int8
+int soft_bits(const polar_sc_plan *p) { return p->cfg.llr_bits > 8 ? 16 : 8; }
+
+// the fused kernel of `dtype` on the current device (st->soft_fn[dtype] stays null for a plan or
+// type that decodes with two launches)
+int ensure_soft(const polar_sc_plan *p, int dtype, DevState **out)
+{
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return hip_fail("hipGetDevice", e);
+    std::lock_guard<std::mutex> lk(p->mu);
+    DevState &st = p->dev[dev];
+    *out = &st;
+    return polar_host::soft_load(*p, st, dtype);
+}
+
 // The per-op monitor (the analogue of the reference's sc_monitor latency report,
 // src/rtl_simu_testbench/sc_monitor/sc_monitor.h:50-140, fed by my_module's Fct_ID / N_value
 // ports, my_module.h:21-30): one decode with the traced interpreter (hybrid plans: the
@@ -1167,6 +1194,8 @@ int polar_sc_plan_destroy(polar_sc_plan *p)
         if (kv.second.module) (void)hipModuleUnload(kv.second.module);
         if (kv.second.imodule) (void)hipModuleUnload(kv.second.imodule);
         if (kv.second.module16) (void)hipModuleUnload(kv.second.module16);
+        for (hipModule_t sm : kv.second.soft_module)
+            if (sm) (void)hipModuleUnload(sm);
         if (kv.second.ops16) (void)hipFree(kv.second.ops16);
         if (kv.second.scratch) (void)hipFree(kv.second.scratch);
         if (kv.second.wide) (void)hipFree(kv.second.wide);
@@ -1209,6 +1238,59 @@ int polar_sc_decode_info(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t
     if (!p || (batch > 0 && (!llr_dev || !xhat_dev || (p->K > 0 && !info_dev)))) return -EINVAL;
     if (const int rc = polar_sc_decode(p, llr_dev, xhat_dev, batch, stream)) return rc;
     return xform_common(p, 0, xhat_dev, info_dev, batch, stream);
+}
+
+int polar_sc_quantize(const void *v_dev, int dtype, size_t n, int beta, int vsatn, int vsatp, void *q_dev, int bits,
+                      void *stream)
+{
+    if ((bits != 8 && bits != 16) || !quant_args_ok(dtype, beta, vsatn, vsatp, bits)) return -EINVAL;
+    if (n == 0) return 0;
+    if (!v_dev || !q_dev || !elem_aligned(v_dev, dtype) || ((uintptr_t)q_dev & (bits == 16 ? 1u : 0u))) return -EINVAL;
+    const int rc = polar_sc_launch_quantize(v_dev, dtype, n, beta, vsatn, vsatp, q_dev, bits, stream);
+    return rc ? hip_fail("quantizer launch", (hipError_t)rc) : 0;
+}
+
+int polar_sc_soft_info_get(const polar_sc_plan *p, int dtype, size_t batch, polar_sc_soft_info *info)
+{
+    if (!p || !info || dtype < POLAR_SC_F32 || dtype > POLAR_SC_BF16 || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    polar_sc_soft_info r{};
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (const int rc = polar_host::soft_compile(*p, dtype)) return rc;
+        r.regs = (uint32_t)p->soft_regs[dtype];
+        r.fused = r.regs ? 1u : 0u;
+        if (r.fused) r.code_key = polar_host::code_key(p->soft_code[dtype]);
+    }
+    if (!r.fused) r.workspace_bytes = (uint64_t)batch * p->N * (uint64_t)(soft_bits(p) / 8);
+    *info = r;
+    return 0;
+}
+
+int polar_sc_decode_soft(const polar_sc_plan *p, const void *v_dev, int dtype, int beta, int vsatn, int vsatp,
+                         void *workspace, uint64_t *hard_bits_dev, size_t batch, void *stream)
+{
+    if (!p || !quant_args_ok(dtype, beta, vsatn, vsatp, soft_bits(p))) return -EINVAL;
+    if (batch == 0) return 0;
+    if (!v_dev || !hard_bits_dev || !elem_aligned(v_dev, dtype) || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    bool fused;   // (host only: the arguments are judged before the device is touched)
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (const int rc = polar_host::soft_compile(*p, dtype)) return rc;
+        fused = p->soft_regs[dtype] > 0;
+    }
+    if (fused) {
+        DevState *st = nullptr;
+        if (const int rc = ensure_soft(p, dtype, &st)) return rc;
+        return polar_host::soft_launch(*st, dtype, v_dev, (float)beta, vsatn, vsatp, (uint16_t *)hard_bits_dev,
+                                       (long)batch, (int)(4 * ((p->G + 3) / 4)), stream);
+    }
+    // two launches: the quantizer into the caller's workspace, then the plan's own decode
+    if (!workspace || ((uintptr_t)workspace & 15u)) return -EINVAL;
+    const int bits = soft_bits(p);
+    if (const int rc = polar_sc_quantize(v_dev, dtype, batch * (size_t)p->N, beta, vsatn, vsatp, workspace, bits, stream))
+        return rc;
+    return bits == 16 ? polar_sc_decode_i16(p, (const int16_t *)workspace, hard_bits_dev, batch, stream)
+                      : polar_sc_decode(p, (const int8_t *)workspace, hard_bits_dev, batch, stream);
 }
 
 int polar_sc_decode(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *hard_bits_dev,

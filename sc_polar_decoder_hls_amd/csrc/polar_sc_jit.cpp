@@ -51,6 +51,7 @@ namespace {
 #include "polar_sc_device_src.inc"   // kPolarDeviceSrc: polar_sc_device.h as a string
 #include "polar_sc_interp_src.inc"   // kPolarInterpSrc: polar_sc_interp.h as a string
 #include "polar_sc_pair_src.inc"     // kPolarPairSrc: polar_sc_pair.h as a string
+#include "polar_sc_quant_src.inc"    // kPolarQuantSrc: polar_sc_quant.h as a string (soft kernels only)
 }
 
 namespace polar_host {
@@ -697,7 +698,10 @@ struct Gen {
         o << "}\n\n";
     }
 
-    std::string run_mask(const polar_sc_plan &p)
+    // soft >= 0 (POLAR_SC_F32 / F16 / BF16): the kernel of polar_sc_decode_soft for that input
+    // type, polar_sc_mask_soft_kernel. It differs from the int8 kernel in its arguments and in how
+    // the stage image is filled (soft_stage); from the wave barrier on the text is the same.
+    std::string run_mask(const polar_sc_plan &p, int soft = -1)
     {
         const int N = (int)p.N, G = (int)p.G;
         // Channel staging: each wave copies its 8 frames (8 x N bytes, contiguous rows of the
@@ -713,12 +717,15 @@ struct Gen {
         o << "#define POLAR_LANE_REMAP 1\n#define POLAR_Q " << p.cfg.llr_bits << "\n"
           << (p.cfg.extended ? "" : "#define POLAR_EXT 0\n")   // EXTENDED = 0: saturating leaves
           << "#include \"polar_sc_device.h\"\nusing namespace polar;\n"
-          << kRepCarrySrc << kMaskFormsSrc
-          << "typedef const __attribute__((address_space(1))) void *gas_t;\n"
+          << kRepCarrySrc << kMaskFormsSrc;
+        if (soft >= 0) o << kPolarQuantSrc;
+        o << "typedef const __attribute__((address_space(1))) void *gas_t;\n"
           << "typedef __attribute__((address_space(3))) void *las_t;\n"
-          << "extern \"C\" __global__ void __launch_bounds__(" << 64 * wpb << ", " << MASK_MIN_WAVES
-          << ") polar_sc_mask_kernel(\n"
-          << "    const unsigned char *__restrict__ llr, unsigned short *__restrict__ out, int batch, int out_stride)\n{\n"
+          << "extern \"C\" __global__ void __launch_bounds__(" << 64 * wpb << ", " << MASK_MIN_WAVES << ") "
+          << (soft >= 0 ? "polar_sc_mask_soft_kernel(\n    const void *__restrict__ v, unsigned short *__restrict__ out, "
+                          "int batch, int out_stride, float beta, int vsatn, int vsatp)\n{\n"
+                        : "polar_sc_mask_kernel(\n    const unsigned char *__restrict__ llr, unsigned short "
+                          "*__restrict__ out, int batch, int out_stride)\n{\n")
           << "  __shared__ uint4 stage_[" << wpb << " * 8 * " << FS / 16 << "];\n"
           // channel byte -> SM8 (qconv_format; bit 7 sign), and -> |LLR|, sign for the unpacked root
           << "  __shared__ unsigned char tab8_[256], tabm_[256], tabs_[256];\n"
@@ -739,8 +746,12 @@ struct Gen {
           << "  long wave = (long)blockIdx.x * " << wpb << " + wib;\n"
           << "#endif\n"
           << "  if (wave >= nw_) return;\n"
-          << "  unsigned char *st_ = (unsigned char *)stage_ + wib * " << 8 * FS << ";\n"
-          << "  const bool al_ = (((unsigned long)llr) & 15u) == 0u;\n"
+          << "  unsigned char *st_ = (unsigned char *)stage_ + wib * " << 8 * FS << ";\n";
+        if (soft >= 0) {
+            soft_stage(N, FS, soft);
+            return mask_decode(G);
+        }
+        o << "  const bool al_ = (((unsigned long)llr) & 15u) == 0u;\n"
           << "  const unsigned char *lla_ = (const unsigned char *)((unsigned long)llr & ~15ul);   // 16-byte aligned\n"
           // async HBM -> LDS copy of the 8 frames of batch w, frames past the batch clamped to
           // the last one. Uniform frame base (SGPR) + lane offset: one VGPR for all eight
@@ -795,8 +806,80 @@ struct Gen {
           << "      const long fr = wave * 8 + f < batch ? wave * 8 + f : (long)batch - 1;\n"
           << "      st_[f * " << FS << " + off] = llr[fr * " << N << " + off];\n"
           << "    }\n"
-          << "  }\n"
-          << "  __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\");\n"
+          << "  }\n";
+        return mask_decode(G);
+    }
+
+    // The stage image of polar_sc_decode_soft: the wave's 8 frames of float / half / bfloat16
+    // values, quantized in registers (polar_sc_quant.h, as polar_sc_soft.hip does) and written as
+    // the packed int8 bytes the async copy of the int8 kernel leaves there: byte i of frame f at
+    // f * FS + i. A lane takes the 16-value chunk `lane` (+ 64 c) of a frame: ES 16-byte loads (4 for
+    // fp32, 2 for the 16-bit types) from the wave-uniform frame base (SGPRs, frames past the batch
+    // clamped to the last one) plus its own 32-bit offset, and one ds_write_b128. Loads are issued
+    // in blocks of 8 (32 VGPRs: 2 frames of fp32 at N = 1024, 4 of a 16-bit type), then converted
+    // and written chunk by chunk, with a scheduling fence after each: all 32 loads of fp32 in
+    // flight at once would not fit, blocks of 16 spilled at N = 128 (half, 128 VGPRs and scratch),
+    // and the registers are dead before the decode begins (the block scope).
+    // An input that is not 16-byte aligned is read element by element, as the int8 kernel's
+    // byte copy; both forms sit in front of the decode, not inside it (a branch in the middle of
+    // the straight-line code costs the register allocator ~100 VGPRs).
+    void soft_stage(int N, int FS, int soft)
+    {
+        const int LPF = N / 16, ES = soft == 0 ? 4 : 2;   // chunks per frame, bytes per value
+        struct Unit { int f, c; };
+        std::vector<Unit> units;
+        for (int f = 0; f < 8; f++)
+            for (int c = 0; c < (LPF + 63) / 64; c++) units.push_back({f, c});
+        const size_t per_block = 8 / ES;
+        o << "  const bool al_ = (((unsigned long)v) & 15u) == 0u;\n"
+          << "  const unsigned char *vb_ = (const unsigned char *)v;\n"
+          << "  {\n"
+          << "  int lane = threadIdx.x & 63;\n"
+          << "  asm volatile(\"\" : \"+v\"(lane));\n"
+          << "  const int row = lane >> 4, pl = lane & 15;\n"
+          << "  Lanes ln; ln.init((u32)pl);\n"
+          << "  const unsigned char *chl = st_ + row * " << FS << " + ln.pos, *chh = st_ + (row + 4) * " << FS
+          << " + ln.pos;\n"
+          << "  if (al_) {\n"
+          << "    const u32 f0_ = wave * 8u, fl_ = (u32)batch - 1u, lo_ = (u32)lane * " << 16 * ES << "u;\n";
+        for (size_t b0 = 0; b0 < units.size(); b0 += per_block) {
+            const size_t b1 = std::min(units.size(), b0 + per_block);
+            o << "    { uint4 r_[" << (b1 - b0) * ES << "];\n";
+            for (size_t u = b0; u < b1; u++) {
+                const int f = units[u].f, c = units[u].c;
+                const std::string pred = LPF - c * 64 >= 64 ? "" : "if (lane < " + std::to_string(LPF - c * 64) + ") ";
+                o << "      { const u32 fr_ = (u32)__builtin_amdgcn_readfirstlane((int)__builtin_elementwise_min(f0_ + " << f
+                  << "u, fl_));\n"
+                  << "        const uint4 *p_ = (const uint4 *)(vb_ + ((size_t)fr_ * " << (size_t)N * ES << " + "
+                  << (size_t)c * 1024 * ES << ") + (size_t)lo_);\n        " << pred << "{";
+                for (int j = 0; j < ES; j++) o << " r_[" << (u - b0) * ES + j << "] = p_[" << j << "];";
+                o << " } }\n";
+            }
+            fence();
+            for (size_t u = b0; u < b1; u++) {
+                const int f = units[u].f, c = units[u].c;
+                const std::string pred = LPF - c * 64 >= 64 ? "" : "if (lane < " + std::to_string(LPF - c * 64) + ") ";
+                o << "      " << pred << "*(uint4 *)(st_ + " << f * FS + c * 1024 << " + lane * 16) = polar_quant::quant_vec<" << soft
+                  << ", 8>(r_ + " << (u - b0) * ES << ", beta, vsatn, vsatp);\n";
+                fence();   // (one chunk's 16 values at a time: converted together they spill)
+            }
+            o << "    }\n";
+        }
+        o << "  } else {   // input not 16-byte aligned: element loads\n"
+          << "    for (int q = lane; q < " << 8 * N << "; q += 64) {\n"
+          << "      const int f = q / " << N << ", off = q % " << N << ";\n"
+          << "      const long fr = wave * 8 + f < batch ? wave * 8 + f : (long)batch - 1;\n"
+          << "      st_[f * " << FS << " + off] = (unsigned char)polar_quant::quant(polar_quant::load_elem<" << soft
+          << ">(vb_, (unsigned long)(fr * " << N << " + off)), beta, vsatn, vsatp);\n"
+          << "    }\n"
+          << "  }\n";
+    }
+
+    // the per-mask kernel from the point where the wave's stage image is complete (inside the
+    // block that holds lane, row, pl, ln, chl, chh): the decode and the output
+    std::string mask_decode(int G)
+    {
+        o << "  __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\");\n"
           << "  __builtin_amdgcn_wave_barrier();\n"
           << "  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\");\n"
           << "  u32 bw[" << (G >= 16 ? G / 16 : 1) << "] = {};\n";
@@ -962,10 +1045,13 @@ uint64_t source_key(const std::string &src, bool rtc = true)
 // profiles record it and bench.py reuses their counters only for the same machine code.
 uint64_t code_key(const polar_sc_plan &p)
 {
-    const std::vector<char> &code = p.jit_code;
-    if ((!p.jit && !p.hybrid && !p.pair) || code.size() < sizeof(Elf64_Ehdr) ||
-        std::memcmp(code.data(), ELFMAG, SELFMAG) != 0)
-        return 0;
+    if (!p.jit && !p.hybrid && !p.pair) return 0;
+    return code_key(p.jit_code);
+}
+
+uint64_t code_key(const std::vector<char> &code)
+{
+    if (code.size() < sizeof(Elf64_Ehdr) || std::memcmp(code.data(), ELFMAG, SELFMAG) != 0) return 0;
     Elf64_Ehdr eh;
     std::memcpy(&eh, code.data(), sizeof eh);
     if (eh.e_ident[EI_CLASS] != ELFCLASS64 || eh.e_shentsize != sizeof(Elf64_Shdr) || eh.e_shstrndx >= eh.e_shnum ||
@@ -1278,12 +1364,16 @@ int offline_compile(const std::string &src, std::vector<char> &code, std::string
 // whole: a generated kernel source (compiled by the clang driver when available, under its own
 // cache key); otherwise, and for the interpreter sources, hipRTC
 // *compiler (optional): which compiler built the returned object, POLAR_SC_COMPILER_*
+// no_pk_f32: the clang driver builds the object without packed fp32 instructions (the soft
+// kernels, whose only fp32 arithmetic is the quantizer's named multiply)
 int rtc_compile(const std::string &src, std::vector<char> &code, std::string &log, bool whole = false,
-                uint32_t *compiler = nullptr)
+                uint32_t *compiler = nullptr, bool no_pk_f32 = false)
 {
     if (compiler) *compiler = POLAR_SC_COMPILER_HIPRTC;
     if (whole) {
-        const std::vector<std::string> extra = extra_clang_flags();
+        std::vector<std::string> extra = extra_clang_flags();
+        if (no_pk_f32)
+            for (const char *w : {"-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"}) extra.push_back(w);
         std::string key = src + "\n// offline clang driver: " + clang_identity() + "\n";
         for (const std::string &w : extra) key += "// " + w + "\n";
         const std::string opath = cache_path(key, false);
@@ -1296,7 +1386,7 @@ int rtc_compile(const std::string &src, std::vector<char> &code, std::string &lo
             cache_store(opath, code);
             return 0;
         }
-        if (!extra.empty()) {
+        if (!extra_clang_flags().empty()) {
             log += "POLAR_SC_CLANG_FLAGS set: no cached object and no clang driver to build one\n";
             return -EIO;
         }
@@ -1352,6 +1442,65 @@ int jit_compile(const polar_sc_plan &p)
         return -ENOTSUP;
     }
     return rtc_compile(src, p.jit_code, p.jit_log, true, &p.jit_compiler);
+}
+
+// ---- polar_sc_decode_soft on per-mask plans: the fused kernel, one code object per input type
+// (Gen::run_mask soft mode), compiled on the first use of that type and cached under the key of
+// its own source ------------------------------------------------------------------------------
+std::string soft_source(const polar_sc_plan &p, int dtype) { return Gen(p.ops, p.lg).run_mask(p, dtype); }
+
+// Which input types the fused kernel serves. The rule: a type whose fused decode
+// is slower than the quantizer launch followed by the int8 decode, by more than the spread of
+// the interleaved rounds at 65,536 x FB_N1024_K512, takes the two launches.
+constexpr bool kSoftFuse[3] = {true, true, true};   // POLAR_SC_F32, F16, BF16
+
+// p.soft_regs[dtype]: registers per lane of the fused kernel; 0 when this plan and type decode
+// with two launches (not a per-mask plan, the type's rule above, or an object whose waves do not
+// fit MASK_WPB per block, which jit_launch's shape needs). Under the plan lock.
+int soft_compile(const polar_sc_plan &p, int dtype)
+{
+    if (p.soft_regs[dtype] >= 0) return 0;
+    if (!p.jit || !kSoftFuse[dtype]) {
+        p.soft_regs[dtype] = 0;
+        return 0;
+    }
+    if (const int rc = rtc_compile(soft_source(p, dtype), p.soft_code[dtype], p.jit_log, true, nullptr, true)) return rc;
+    const int regs = kernel_regs(p.soft_code[dtype], "polar_sc_mask_soft_kernel");
+    if (regs < 0) return -EIO;
+    p.soft_regs[dtype] = fit_waves(regs, MASK_WPB) == MASK_WPB ? regs : 0;
+    return 0;
+}
+
+int soft_load(const polar_sc_plan &p, DevState &st, int dtype)
+{
+    if (st.soft_fn[dtype]) return 0;
+    if (const int rc = soft_compile(p, dtype)) {
+        std::fprintf(stderr, "polar_sc: soft kernel build failed (%d)%s%s\n", rc, p.jit_log.empty() ? "" : ":\n",
+                     p.jit_log.c_str());
+        return rc;
+    }
+    if (p.soft_regs[dtype] == 0) return 0;   // two launches
+    if (hipError_t e = hipModuleLoadData(&st.soft_module[dtype], p.soft_code[dtype].data()); e != hipSuccess) {
+        std::fprintf(stderr, "polar_sc: hipModuleLoadData: %s\n", hipGetErrorString(e));
+        return -EIO;
+    }
+    if (hipModuleGetFunction(&st.soft_fn[dtype], st.soft_module[dtype], "polar_sc_mask_soft_kernel") != hipSuccess)
+        return -EIO;
+    return 0;
+}
+
+// the launch shape of jit_launch: one wave per 8 frames, MASK_WPB waves per block
+int soft_launch(const DevState &st, int dtype, const void *v, float beta, int vsatn, int vsatp, uint16_t *out,
+                long batch, int out_stride, void *stream)
+{
+    const long waves = (batch + 7) / 8;
+    const unsigned blocks = (unsigned)((waves + MASK_WPB - 1) / MASK_WPB);
+    int b = (int)batch;
+    void *args[] = {(void *)&v, (void *)&out, (void *)&b, (void *)&out_stride, (void *)&beta, (void *)&vsatn,
+                    (void *)&vsatp};
+    hipError_t e = hipModuleLaunchKernel(st.soft_fn[dtype], blocks, 1, 1, 64 * MASK_WPB, 1, 1, 0, (hipStream_t)stream,
+                                         args, nullptr);
+    return e == hipSuccess ? 0 : -EIO;
 }
 
 // Per-mask plans whose LLR_BITS is not the hipcc-built 6: the per-op monitor runs the schedule

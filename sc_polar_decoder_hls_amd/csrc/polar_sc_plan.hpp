@@ -33,6 +33,10 @@ struct DevState {
     hipFunction_t fn16 = nullptr;
     void *ops16 = nullptr;              //   and its schedule when it differs from `ops`
     void *xtab = nullptr;               // per-dword mask table of the transform kernels (polar_sc_xform.hip)
+    // polar_sc_decode_soft on per-mask plans: the fused kernel per input type (POLAR_SC_F32 /
+    // F16 / BF16), loaded by the first soft decode of that type on this device
+    hipModule_t soft_module[3] = {nullptr, nullptr, nullptr};
+    hipFunction_t soft_fn[3] = {nullptr, nullptr, nullptr};
     int simds = 0;                // SIMDs of the device (4 per CU), for launch sizing
     // registers per lane (VGPR + AGPR allocation, kernel descriptor) of the generated decode
     // kernel and of the pair segment kernel: the launch shape is capped so that a block's
@@ -177,6 +181,10 @@ struct polar_sc_plan {
     mutable uint32_t jit_compiler = 0;    // POLAR_SC_COMPILER_* of jit_code
     mutable std::vector<char> interp_code;   // per-mask plans, llr_bits != 6: traced interpreter
     mutable std::vector<char> code16;        // interpreter on the int16 channel (polar_sc_decode_i16)
+    // polar_sc_decode_soft: the fused per-mask kernel per input type and its registers per lane
+    // (-1: not built yet; 0: this plan and type decode with two launches)
+    mutable std::vector<char> soft_code[3];
+    mutable int soft_regs[3] = {-1, -1, -1};
     mutable std::string jit_log;
 };
 
@@ -205,4 +213,11 @@ void code_regs(const polar_sc_plan &p, int &regs, int &regs_seg);
 constexpr int MASK_WAVES_PER_BLOCK = 4;   // per-mask kernel launch (polar_sc_jit.cpp MASK_WPB)
 PairShape pair_shape(const polar_sc_plan &p, long batch, int simds, int regs, int regs_seg);
 uint64_t code_key(const polar_sc_plan &p);   // hash of the compiled kernels' instructions + descriptors (0: none)
+uint64_t code_key(const std::vector<char> &code);   // the same of one code object
+// polar_sc_decode_soft on per-mask plans (polar_sc_jit.cpp): the fused kernel of one input type
+std::string soft_source(const polar_sc_plan &p, int dtype);
+int soft_compile(const polar_sc_plan &p, int dtype);   // fills p.soft_code / p.soft_regs (host only, idempotent)
+int soft_load(const polar_sc_plan &p, DevState &st, int dtype);
+int soft_launch(const DevState &st, int dtype, const void *v, float beta, int vsatn, int vsatp, uint16_t *out,
+                long batch, int out_stride, void *stream);
 }  // namespace polar_host
