@@ -349,6 +349,44 @@ int polar_sc_decode_soft(const polar_sc_plan *plan, const void *v_dev, int dtype
                          int vsatn, int vsatp, void *workspace, uint64_t *hard_bits_dev,
                          size_t batch, void *stream);
 
+/* ---- Channel values straight to information words ----
+ * One call from int8 LLRs or float channel values to the information words of
+ * polar_sc_extract_info ([batch][ceil(K/64)] uint64, every word written). Per-mask plans
+ * (N <= 1024) do it in one launch: the decode kernel transforms and compresses the x^ it holds
+ * in registers, and x^ never reaches memory. Every other plan decodes into the caller's
+ * workspace and extracts from there on the same stream. `input`: one of POLAR_SC_F32 / F16 /
+ * BF16, or POLAR_SC_I8 for int8 LLRs. */
+enum { POLAR_SC_I8 = 3 };
+
+typedef struct polar_sc_to_info {
+    uint32_t fused;            /* 1: one launch; 0: the decode into the workspace, then the extraction */
+    uint32_t regs;             /* registers per lane of the one-launch kernel, else 0 */
+    uint64_t workspace_bytes;  /* bytes the caller must pass as workspace for `batch` frames: 0 when
+                                  fused, else the x^ rows, batch * ceil(N/64) * 8, plus for a float
+                                  input the workspace_bytes of polar_sc_soft_info_get, the whole
+                                  rounded up to 16 */
+    uint64_t code_key;         /* as polar_sc_launch_info.code_key, of the one-launch kernel */
+} polar_sc_to_info;
+
+/* Host only. Compiles the one-launch kernel of `input` if needed (and, where a float input takes
+ * the workspace path, what polar_sc_soft_info_get compiles). */
+int polar_sc_to_info_get(const polar_sc_plan *plan, int input, size_t batch, polar_sc_to_info *out);
+
+/* int8 LLRs llr_dev[batch][N] -> info_dev. workspace: at least workspace_bytes of
+ * polar_sc_to_info_get(plan, POLAR_SC_I8, batch), 16-byte aligned, contents unspecified
+ * afterwards; may be NULL when that is 0. The first call on a device loads the kernel
+ * synchronously (the workspace path: uploads the mask table); later calls allocate nothing and
+ * can be captured in a graph. Asynchronous on `stream`; batch == 0 returns 0, K == 0 launches
+ * nothing; batch <= 2^31 - 8. */
+int polar_sc_decode_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, void *workspace,
+                            uint64_t *info_dev, size_t batch, void *stream);
+
+/* The same from float channel values v_dev[batch][N], quantized as polar_sc_decode_soft does
+ * (its argument rules); workspace as above for `dtype`. */
+int polar_sc_decode_soft_to_info(const polar_sc_plan *plan, const void *v_dev, int dtype, int beta,
+                                 int vsatn, int vsatp, void *workspace, uint64_t *info_dev,
+                                 size_t batch, void *stream);
+
 int polar_sc_plan_get_stats(const polar_sc_plan *plan, polar_sc_plan_stats *stats);
 
 /* Copy the compiled schedule (at most cap ops) and its length. */

@@ -108,8 +108,13 @@ class polar_sc_soft_info(ctypes.Structure):
                 ("code_key", ctypes.c_uint64)]
 
 
+class polar_sc_to_info(ctypes.Structure):
+    _fields_ = polar_sc_soft_info._fields_
+
+
 # POLAR_SC_F32 / F16 / BF16 by torch dtype name (float channel values, include/polar_sc.h)
 SOFT_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+POLAR_SC_I8 = 3      # int8 LLRs as the input of decode_to_info
 
 
 # exported symbols of include/polar_sc.h (tests check that the library exports all of them)
@@ -125,6 +130,7 @@ EXPORTS = (
     "polar_sc_trace", "polar_sc_decode_i16", "polar_sc_debug_subtree", "polar_sc_plan_launch_info",
     "polar_sc_extract_info", "polar_sc_encode", "polar_sc_decode_info", "polar_info_to_codeword",
     "polar_sc_quantize", "polar_sc_soft_info_get", "polar_sc_decode_soft",
+    "polar_sc_to_info_get", "polar_sc_decode_to_info", "polar_sc_decode_soft_to_info",
 )
 
 _lib = None
@@ -167,6 +173,9 @@ def lib():
         "polar_sc_quantize": [p, i32, sz, i32, i32, i32, p, i32, p],
         "polar_sc_soft_info_get": [p, i32, sz, p],
         "polar_sc_decode_soft": [p, p, i32, i32, i32, i32, p, p, sz, p],
+        "polar_sc_to_info_get": [p, i32, sz, p],
+        "polar_sc_decode_to_info": [p, p, p, p, sz, p],
+        "polar_sc_decode_soft_to_info": [p, p, i32, i32, i32, i32, p, p, sz, p],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
         "polar_sc_selftest_lanes": [p],
@@ -577,6 +586,60 @@ class Decoder:
                 ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(s.cuda_stream)))
         return out
 
+    # -- channel values straight to information words ---------------------------
+    def to_info_path(self, dtype, batch):
+        """How decode_to_info() of `batch` frames of `dtype` (torch.int8 or a torch float dtype)
+        runs, as a dict: fused (1: one launch), regs, workspace_bytes, code_key (16 hex digits).
+        Host only; compiles the kernel if needed."""
+        r = polar_sc_to_info()
+        _check("polar_sc_to_info_get", lib().polar_sc_to_info_get(self._plan, _to_info_input(dtype), int(batch),
+                                                                  ctypes.byref(r)))
+        d = {f: getattr(r, f) for f, _ in polar_sc_to_info._fields_}
+        d["code_key"] = "%016x" % r.code_key
+        return d
+
+    def decode_to_info(self, x, beta=4, vsatn=None, vsatp=None, out=None, workspace=None, stream=None):
+        """Frames [B, N] -> information words [B, info_words] (the rows of extract_info) in one call:
+        x an int8 CUDA tensor of LLRs, or float32 / float16 / bfloat16 channel values quantized as
+        decode_soft does (beta, vsatn, vsatp: its arguments, unused for int8). Per-mask plans
+        (N <= 1024) run one kernel and never write the codeword estimate; others need a workspace of
+        to_info_path()["workspace_bytes"] bytes (a uint8 CUDA tensor, 16-byte aligned), allocated
+        here when not given. Asynchronous on `stream`."""
+        torch = _torch()
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise TypeError("x must be a CUDA int8, float32, float16 or bfloat16 tensor")
+        inp = _to_info_input(x.dtype)
+        if x.dim() != 2 or x.shape[1] != self.N or not x.is_contiguous():
+            raise ValueError("x must be contiguous [B, %d]" % self.N)
+        B = x.shape[0]
+        lim = (1 << (self.llr_bits - 1)) - 1
+        vsatn = -lim if vsatn is None else int(vsatn)
+        vsatp = lim if vsatp is None else int(vsatp)
+        if out is None:
+            out = torch.empty((B, self.info_words), dtype=torch.int64, device=x.device)
+        else:
+            self._check_out(out, x, (B, self.info_words), torch.int64)
+        need = self.to_info_path(x.dtype, B)["workspace_bytes"] if B else 0
+        if need and workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        if workspace is not None:
+            if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous()
+                    and workspace.device == x.device):
+                raise ValueError("workspace must be a contiguous CUDA tensor on the device of x")
+            if workspace.numel() * workspace.element_size() < need:
+                raise ValueError("workspace must hold %d bytes" % need)
+        ws = ctypes.c_void_p(workspace.data_ptr()) if workspace is not None else None
+        with torch.cuda.device(x.device):
+            s = stream if stream is not None else torch.cuda.current_stream(x.device)
+            ptrs = (ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(s.cuda_stream))
+            if inp == POLAR_SC_I8:
+                _check("polar_sc_decode_to_info", lib().polar_sc_decode_to_info(
+                    self._plan, ctypes.c_void_p(x.data_ptr()), ws, *ptrs))
+            else:
+                _check("polar_sc_decode_soft_to_info", lib().polar_sc_decode_soft_to_info(
+                    self._plan, ctypes.c_void_p(x.data_ptr()), inp, int(beta), vsatn, vsatp, ws, *ptrs))
+        return out
+
     # -- information bits on the device (DESIGN.md 3.8) ----------------------------------------
     def _xform(self, fn, src, cols_in, cols_out, out, stream, name):
         torch = _torch()
@@ -641,6 +704,13 @@ def _soft_dtype(dtype):
     if name not in SOFT_DTYPES:
         raise TypeError("channel values must be float32, float16 or bfloat16, not %s" % dtype)
     return SOFT_DTYPES[name]
+
+
+def _to_info_input(dtype):
+    """torch.int8 (or its name, or the POLAR_SC_* code) -> POLAR_SC_I8; else as _soft_dtype"""
+    if not isinstance(dtype, int) and str(dtype).replace("torch.", "") == "int8":
+        return POLAR_SC_I8
+    return _soft_dtype(dtype)
 
 
 def quantize(v, beta=4, vsatn=-31, vsatp=31, bits=8, out=None, stream=None):

@@ -136,6 +136,8 @@ def _compile_item(item):
     ok = dec.compile()
     for dt in item[4] if len(item) > 4 else ():   # the fused kernels of decode_soft (_plansets.soft_items)
         dec.soft_info(dt, 8)
+    for dt in item[5] if len(item) > 5 else ():   # the kernels of decode_to_info (_plansets.info_items)
+        dec.to_info_path(dt, 8)
     dec.close()
     return name, tun, ok, time.time() - t0
 
@@ -211,6 +213,7 @@ def _default_procs():
 
 def prewarm_items(items, procs=None, verbose=False):
     """Compile the hipRTC kernels of [(name, info mask, config fields dict or None, tuning dict
-    or None[, input types whose decode_soft kernels to build too])] into the code-object cache
+    or None[, input types whose decode_soft kernels to build too[, inputs whose decode_to_info
+    kernels to build]])] into the code-object cache
     (host only, in parallel)."""
     _run_pool(list(items), procs or _default_procs(), verbose)

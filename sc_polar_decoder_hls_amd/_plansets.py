@@ -448,6 +448,20 @@ def soft_items():
          ("frozen_n_2048_k_1024", mask("frozen_n_2048_k_1024"), {"llr_bits": 9}, None, ())]
 
 
+# ---- channel values straight to information words (tests/test_to_info.py, tests/test_to_info_gpu.py,
+# tools/to_info_speed.py): the plans whose one-launch kernels (one per input, Decoder.to_info_path)
+# they decode with; the workspace path's plan (frozen_n_2048_k_1024) is compiled with all_items() -----
+INFO_INT8_MASKS = ("spc_n32", "FB_N128_K64", "FB_N256_K128", "FB_N512_K256", "FB_N1024_K512", "frozen_n_1024_k_922")
+INFO_FLOAT_MASKS = ("FB_N128_K64", "frozen_n_1024_k_922")
+
+
+def info_items():
+    """(name, mask, config fields, tuning, input types of the decode_soft kernels the float cases
+    compare with, inputs of the decode_to_info kernels to build)"""
+    floats = {n: SOFT_DTYPES if n in INFO_FLOAT_MASKS + ("FB_N1024_K512",) else () for n in INFO_INT8_MASKS}
+    return [(n, soft_mask(n), None, None, floats[n], ("int8",) + floats[n]) for n in INFO_INT8_MASKS]
+
+
 def prewarm_all(verbose=False):
     """Compile every plan of all_items() into lib/rtc_cache/: each distinct plan once, all of
     them in one pool of worker processes (a clean build compiles ~650 kernels, hours of one
@@ -478,6 +492,7 @@ def prewarm_all(verbose=False):
     _build.prewarm_items(first, verbose=verbose)
     _build.prewarm_items(second, verbose=verbose)
     _build.prewarm_items(soft_items(), verbose=verbose)   # (after their int8 plans: the same masks)
+    _build.prewarm_items(info_items(), verbose=verbose)
 
 
 # ---- high-rate codes across the formats (tests/test_gpu_formats.py

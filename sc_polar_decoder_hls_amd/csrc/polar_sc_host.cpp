@@ -1196,6 +1196,8 @@ int polar_sc_plan_destroy(polar_sc_plan *p)
         if (kv.second.module16) (void)hipModuleUnload(kv.second.module16);
         for (hipModule_t sm : kv.second.soft_module)
             if (sm) (void)hipModuleUnload(sm);
+        for (hipModule_t im : kv.second.info_module)
+            if (im) (void)hipModuleUnload(im);
         if (kv.second.ops16) (void)hipFree(kv.second.ops16);
         if (kv.second.scratch) (void)hipFree(kv.second.scratch);
         if (kv.second.wide) (void)hipFree(kv.second.wide);
@@ -1291,6 +1293,84 @@ int polar_sc_decode_soft(const polar_sc_plan *p, const void *v_dev, int dtype, i
         return rc;
     return bits == 16 ? polar_sc_decode_i16(p, (const int16_t *)workspace, hard_bits_dev, batch, stream)
                       : polar_sc_decode(p, (const int8_t *)workspace, hard_bits_dev, batch, stream);
+}
+
+// ---- channel values straight to information words (include/polar_sc.h) ----------
+int polar_sc_to_info_get(const polar_sc_plan *p, int input, size_t batch, polar_sc_to_info *out)
+{
+    if (!p || !out || input < POLAR_SC_F32 || input > POLAR_SC_I8 || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    polar_sc_to_info r{};
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (const int rc = polar_host::info_compile(*p, input)) return rc;
+        r.regs = (uint32_t)p->info_regs[input];
+        r.fused = r.regs ? 1u : 0u;
+        if (r.fused) r.code_key = polar_host::code_key(p->info_code[input]);
+    }
+    if (!r.fused) {
+        r.workspace_bytes = (uint64_t)batch * ((p->N + 63u) / 64u) * 8u;
+        if (input != POLAR_SC_I8) {
+            polar_sc_soft_info si{};
+            if (const int rc = polar_sc_soft_info_get(p, input, batch, &si)) return rc;
+            r.workspace_bytes = ((r.workspace_bytes + 15u) & ~(uint64_t)15u) + si.workspace_bytes;
+        }
+        r.workspace_bytes = (r.workspace_bytes + 15u) & ~(uint64_t)15u;
+    }
+    *out = r;
+    return 0;
+}
+
+namespace {
+// both entry points: v = int8 LLRs (input POLAR_SC_I8) or float channel values
+int to_info_common(const polar_sc_plan *p, const void *v, int input, int beta, int vsatn, int vsatp, void *workspace,
+                   uint64_t *info, size_t batch, void *stream)
+{
+    if (batch == 0) return 0;
+    if (!v || (p->K > 0 && !info) || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    if (p->K == 0) return 0;   // no information bit: nothing to write, nothing to launch
+    bool fused;   // (host only: the arguments are judged before the device is touched)
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (const int rc = polar_host::info_compile(*p, input)) return rc;
+        fused = p->info_regs[input] > 0;
+    }
+    if (fused) {
+        int dev = 0;
+        if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return hip_fail("hipGetDevice", e);
+        DevState *st = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(p->mu);
+            st = &p->dev[dev];
+            if (const int rc = polar_host::info_load(*p, *st, input)) return rc;
+        }
+        return polar_host::info_launch(*st, input, v, (float)beta, vsatn, vsatp, info, (long)batch,
+                                       (int)((p->K + 63u) / 64u), stream);
+    }
+    // the x^ rows at the start of the caller's workspace, a float input's quantized frames after them
+    if (!workspace || ((uintptr_t)workspace & 15u)) return -EINVAL;
+    uint64_t *xhat = (uint64_t *)workspace;
+    const size_t xbytes = (batch * (size_t)((p->N + 63u) / 64u) * 8u + 15u) & ~(size_t)15u;
+    const int rc = input == POLAR_SC_I8
+                       ? polar_sc_decode(p, (const int8_t *)v, xhat, batch, stream)
+                       : polar_sc_decode_soft(p, v, input, beta, vsatn, vsatp, (char *)workspace + xbytes, xhat, batch, stream);
+    if (rc) return rc;
+    return xform_common(p, 0, xhat, info, batch, stream);
+}
+}  // namespace
+
+int polar_sc_decode_to_info(const polar_sc_plan *p, const int8_t *llr_dev, void *workspace, uint64_t *info_dev,
+                            size_t batch, void *stream)
+{
+    if (!p) return -EINVAL;
+    return to_info_common(p, llr_dev, POLAR_SC_I8, 1, 0, 0, workspace, info_dev, batch, stream);
+}
+
+int polar_sc_decode_soft_to_info(const polar_sc_plan *p, const void *v_dev, int dtype, int beta, int vsatn, int vsatp,
+                                 void *workspace, uint64_t *info_dev, size_t batch, void *stream)
+{
+    if (!p || !quant_args_ok(dtype, beta, vsatn, vsatp, soft_bits(p))) return -EINVAL;
+    if (batch > 0 && v_dev && !elem_aligned(v_dev, dtype)) return -EINVAL;
+    return to_info_common(p, v_dev, dtype, beta, vsatn, vsatp, workspace, info_dev, batch, stream);
 }
 
 int polar_sc_decode(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *hard_bits_dev,

@@ -36,6 +36,7 @@ extern char **environ;   // (POSIX: the environment handed to the spawned compil
 #include <cstring>
 #include <fstream>
 #include <sstream>
+#include <stdexcept>
 
 namespace {
 // per-mask kernels: waves per block and the launch bound's minimum waves per SIMD. The
@@ -176,6 +177,9 @@ struct Gen {
     bool pack = false;
     // per-mask kernels: the forms of kMaskFormsSrc
     bool forms = false;
+    // per-mask kernels: the plan whose information bits the kernel writes instead of x^
+    // (info_epilogue); null: the x^ kernels
+    const polar_sc_plan *info = nullptr;
     Gen(const std::vector<polar_sc_op> &ops_, int lg) : ops(ops_), LG(lg) {}
 
     // Partial sums: u32 bw[max(1, G / 16)], dword j = groups 16 j .. 16 j + 15, low frame in
@@ -701,8 +705,11 @@ struct Gen {
     // soft >= 0 (POLAR_SC_F32 / F16 / BF16): the kernel of polar_sc_decode_soft for that input
     // type, polar_sc_mask_soft_kernel. It differs from the int8 kernel in its arguments and in how
     // the stage image is filled (soft_stage); from the wave barrier on the text is the same.
-    std::string run_mask(const polar_sc_plan &p, int soft = -1)
+    // to_info: the same decode with the information-bit epilogue, polar_sc_mask_info_kernel /
+    // polar_sc_mask_soft_info_kernel (info rows and their stride in u64 in place of out / out_stride)
+    std::string run_mask(const polar_sc_plan &p, int soft = -1, bool to_info = false)
     {
+        if (to_info) info = &p;
         const int N = (int)p.N, G = (int)p.G;
         // Channel staging: each wave copies its 8 frames (8 x N bytes, contiguous rows of the
         // [batch][N] input) HBM -> LDS with global_load_lds_dwordx4, then reads the bytes of
@@ -722,10 +729,14 @@ struct Gen {
         o << "typedef const __attribute__((address_space(1))) void *gas_t;\n"
           << "typedef __attribute__((address_space(3))) void *las_t;\n"
           << "extern \"C\" __global__ void __launch_bounds__(" << 64 * wpb << ", " << MASK_MIN_WAVES << ") "
-          << (soft >= 0 ? "polar_sc_mask_soft_kernel(\n    const void *__restrict__ v, unsigned short *__restrict__ out, "
-                          "int batch, int out_stride, float beta, int vsatn, int vsatp)\n{\n"
-                        : "polar_sc_mask_kernel(\n    const unsigned char *__restrict__ llr, unsigned short "
-                          "*__restrict__ out, int batch, int out_stride)\n{\n")
+          << (to_info ? (soft >= 0 ? "polar_sc_mask_soft_info_kernel(\n    const void *__restrict__ v, unsigned long long "
+                                     "*__restrict__ info, int batch, int info_stride, float beta, int vsatn, int vsatp)\n{\n"
+                                   : "polar_sc_mask_info_kernel(\n    const unsigned char *__restrict__ llr, unsigned long "
+                                     "long *__restrict__ info, int batch, int info_stride)\n{\n")
+              : soft >= 0 ? "polar_sc_mask_soft_kernel(\n    const void *__restrict__ v, unsigned short *__restrict__ out, "
+                            "int batch, int out_stride, float beta, int vsatn, int vsatp)\n{\n"
+                          : "polar_sc_mask_kernel(\n    const unsigned char *__restrict__ llr, unsigned short "
+                            "*__restrict__ out, int batch, int out_stride)\n{\n")
           << "  __shared__ uint4 stage_[" << wpb << " * 8 * " << FS / 16 << "];\n"
           // channel byte -> SM8 (qconv_format; bit 7 sign), and -> |LLR|, sign for the unpacked root
           << "  __shared__ unsigned char tab8_[256], tabm_[256], tabs_[256];\n"
@@ -886,6 +897,7 @@ struct Gen {
         stage_arrays(true);
         root_presplit(G);
         all_ops();
+        if (info) return info_epilogue(G);
         // END (my_module.h:1848-1869) + wrapper_out: x^ words in natural order
         // The rows of frames wave * 8 and wave * 8 + 4 are uniform bases (SGPRs); a lane adds one
         // 32-bit byte offset, its row inside the four and its word (out_stride is the plan's G
@@ -925,6 +937,120 @@ struct Gen {
           << "if (st_hi) POLAR_OUTV(o_hi, w_) = 0; }\n"
           << "  }\n";
         o << "}\n";
+        return o.str();
+    }
+
+    // The information-bit epilogue: u^ = x^ F^{(x)n} restricted to the
+    // information positions, packed, from the x^ the wave holds in bw[] -- x^ never reaches HBM.
+    // Order built: the output transpose first, then the transform. After the transpose lane pl of
+    // a row holds word 16 c + pl (codeword bits 16 (16 c + pl) + k at bit k of each half, frames
+    // row / row + 4), and the information bits of a word are then contiguous in the frame's row,
+    // which the compress needs; in the decoder's own layout (lane = bit position inside the word)
+    // the stages would cost the same and the pieces would be strided. The factors of F^{(x)n} commute
+    // (3.8): index bits 8..9 are XORs between the registers (before the transpose: the same XOR on
+    // any layout, and the transposes then overlap them), bits 0..3 shift-mask steps on both halves
+    // at once, bits 4..7 DPP moves between the physical lanes of the row, the lower lane receiving
+    // (polar_sc_xform.hip xf_lane_stage; distances at or above G are left out, those lanes hold no
+    // word). Compress: the parallel-suffix move masks of the lane's 16 mask bits, in both halves, so
+    // that a step serves both frames; with the piece's bit offset in the row they are constants of
+    // the plan, a table indexed by (c, lane) that is read here, through an opaque copy of the lane
+    // index, so that nothing of it is live across the decode. Lanes past G have an empty mask.
+    // Assemble: the wave's 8 rows of IR dwords in its dead stage image (8 (N + 16) bytes; the rows
+    // take at most N, and a piece's second dword at most 8 bytes more): zeroed, each piece ORed in
+    // with LDS atomics (a piece is <= 16 bits at any bit offset: two dwords, the second one zero
+    // when it does not straddle), then stored whole, padding included, with 8-byte vector stores --
+    // the 8 rows are contiguous when info_stride is the row length. Frames past the batch are clamped
+    // copies: assembled, not stored.
+    std::string info_epilogue(int G)
+    {
+        const int C = (G + 15) / 16, K = (int)info->K, R64 = (K + 63) / 64, IR = 2 * R64;
+        if (K <= 0) throw std::runtime_error("information-bit kernel of a plan without information bits");
+        o << "  // END: information bits (transform, compress, rows assembled in LDS, stores)\n"
+          << "  __builtin_amdgcn_sched_barrier(0);\n"
+          // {mask, move masks of distance 1, 2, 4, 8} in both halves, bit offset in its dword, byte
+          // offset of that dword in the row
+          << "  static const __attribute__((aligned(32))) u32 it_[" << 16 * C << "][8] = {\n";
+        uint32_t off = 0;
+        for (int w = 0; w < 16 * C; w++) {
+            uint32_t m = 0, mv[5];
+            if (w < G)
+                for (int i = 0; i < 16; i++) m |= (uint32_t)(info->mask[16 * w + i] != 0) << i;
+            const uint32_t m0 = m, pc = (uint32_t)__builtin_popcount(m);
+            uint32_t mk = ~m << 1;   // (Hacker's Delight 7-4, as polar_sc_xform_table; 16 bits: four steps)
+            for (int i = 0; i < 5; i++) {
+                uint32_t mp = mk ^ (mk << 1);
+                mp ^= mp << 2;
+                mp ^= mp << 4;
+                mp ^= mp << 8;
+                mp ^= mp << 16;
+                mv[i] = mp & m;
+                m = (m ^ mv[i]) | (mv[i] >> (1 << i));
+                mk &= ~mp;
+            }
+            if (mv[4]) throw std::runtime_error("information-bit kernel: 16-bit compress needs a fifth step");
+            const uint32_t o_ = w < G ? off : 0u;
+            o << "    {0x" << std::hex << m0 * 0x10001u << "u, 0x" << mv[0] * 0x10001u << "u, 0x" << mv[1] * 0x10001u << "u, 0x"
+              << mv[2] * 0x10001u << "u, 0x" << mv[3] * 0x10001u << std::dec << "u, " << (o_ & 31u) << "u, " << (o_ >> 5) * 4u
+              << "u, 0u},\n";
+            off += pc;
+        }
+        o << "  };\n"
+          << "  u32 il_ = ln.pl;\n  asm volatile(\"\" : \"+v\"(il_));\n"
+          << "#ifndef POLAR_OUT_TRANSPOSE6\n  OutT ot_; ot_.init(il_);\n"
+          << "#define POLAR_TRANSPOSE16(v) row_transpose16_x(v, ot_)\n"
+          << "#else\n#define POLAR_TRANSPOSE16(v) row_transpose16(v, ln)\n#endif\n"
+          << "  typedef __attribute__((address_space(3))) u32 lu32_t;\n"
+          << "  typedef __attribute__((address_space(3))) unsigned long long lu64_t;\n"
+          << "  typedef __attribute__((address_space(3))) unsigned char lu8_t;\n"
+          << "#define POLAR_WAVE_PHASE() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, \"wavefront\"); "
+             "__builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\"); } while (0)\n"
+          << "#define POLAR_LDS_OR(p, v) (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)\n"
+          << "  lu32_t *const im_ = (lu32_t *)(las_t)st_;   // the wave's stage image: dead since the presplit\n";
+        for (int i = 0; i < 8 * IR; i += 64)
+            o << "  " << (8 * IR - i >= 64 ? std::string() : "if (lane < " + std::to_string(8 * IR - i) + ") ") << "im_[" << i
+              << " + lane] = 0u;\n";
+        o << "  POLAR_WAVE_PHASE();\n"
+          << "  const u32 k1_ = opaque(clear_mask<0>(il_)), k2_ = opaque(clear_mask<1>(il_));\n"
+          << "  u32 x_[" << C << "];\n"
+          // (every record up front: loaded next to its use, each waits for memory on its own)
+          << "  uint4 a_[" << C << "], b_[" << C << "];\n";
+        for (int c = 0; c < C; c++)
+            o << "  a_[" << c << "] = *(const uint4 *)&it_[" << 16 * c << "u + il_][0]; b_[" << c << "] = *(const uint4 *)&it_["
+              << 16 * c << "u + il_][4];\n";
+        for (int c = 0; c < C; c++) o << "  x_[" << c << "] = " << get16(16 * c) << ";\n";
+        for (int h = 1; h < C; h <<= 1)
+            for (int c = 0; c < C; c++)
+                if (!(c & h)) o << "  x_[" << c << "] ^= x_[" << c + h << "];\n";
+        const int L = G < 16 ? G : 16;   // lanes of a row that hold a word
+        for (int c = 0; c < C; c++) {
+            o << "  { u32 w_ = POLAR_TRANSPOSE16(to_position_order(x_[" << c << "], ln));\n"
+              << "    w_ ^= (w_ >> 1) & 0x55555555u; w_ ^= (w_ >> 2) & 0x33333333u;\n"
+              << "    w_ ^= (w_ >> 4) & 0x0F0F0F0Fu; w_ ^= (w_ >> 8) & 0x00FF00FFu;\n";
+            if (L > 1) o << "    w_ ^= xorlane_phys<1>(w_) & k1_;\n";
+            if (L > 2) o << "    w_ ^= xorlane_phys<2>(w_) & k2_;\n";
+            // row_shl:4 into banks 0 and 2, row_shl:8 into banks 0 and 1; the other lanes read 0
+            if (L > 4) o << "    w_ ^= __builtin_amdgcn_update_dpp(0u, w_, 0x104, 0xF, 0x5, false);\n";
+            if (L > 8) o << "    w_ ^= __builtin_amdgcn_update_dpp(0u, w_, 0x108, 0xF, 0x3, false);\n";
+            const std::string a = "a_[" + std::to_string(c) + "]", b = "b_[" + std::to_string(c) + "]";
+            o << "    u32 t_;\n    w_ &= " << a << ".x;\n"
+              << "    t_ = w_ & " << a << ".y; w_ = (w_ ^ t_) | (t_ >> 1);\n"
+              << "    t_ = w_ & " << a << ".z; w_ = (w_ ^ t_) | (t_ >> 2);\n"
+              << "    t_ = w_ & " << a << ".w; w_ = (w_ ^ t_) | (t_ >> 4);\n"
+              << "    t_ = w_ & " << b << ".x; w_ = (w_ ^ t_) | (t_ >> 8);\n"
+              << "    const unsigned long long lo_ = (unsigned long long)(w_ & 0xFFFFu) << " << b << ".y, hi_ = (unsigned long long)(w_ >> 16) << "
+              << b << ".y;\n"
+              << "    lu32_t *const d_ = (lu32_t *)((lu8_t *)im_ + ((u32)row * " << 4 * IR << "u + " << b << ".z));\n"
+              << "    POLAR_LDS_OR(d_, (u32)lo_); POLAR_LDS_OR(d_ + 1, (u32)(lo_ >> 32));\n"
+              << "    POLAR_LDS_OR(d_ + " << 4 * IR << ", (u32)hi_); POLAR_LDS_OR(d_ + " << 4 * IR + 1 << ", (u32)(hi_ >> 32)); }\n";
+        }
+        o << "  POLAR_WAVE_PHASE();\n"
+          << "  const u32 nf_ = (u32)batch - (u32)wave * 8u;\n"
+          << "  unsigned long long *const ob_ = info + (size_t)((u32)wave * 8u) * (u32)info_stride;\n";
+        for (int j = 0; j < 8 * R64; j += 64)
+            o << "  { const u32 j_ = " << j << "u + (u32)lane, f_ = j_ / " << R64 << "u, q_ = j_ - f_ * " << R64 << "u;\n"
+              << "    if (" << (8 * R64 - j >= 64 ? std::string() : "j_ < " + std::to_string(8 * R64) + "u && ")
+              << "f_ < nf_) ob_[(size_t)f_ * (u32)info_stride + q_] = *(const lu64_t *)(im_ + 2u * j_); }\n";
+        o << "  }\n}\n";
         return o.str();
     }
 };
@@ -1499,6 +1625,80 @@ int soft_launch(const DevState &st, int dtype, const void *v, float beta, int vs
     void *args[] = {(void *)&v, (void *)&out, (void *)&b, (void *)&out_stride, (void *)&beta, (void *)&vsatn,
                     (void *)&vsatp};
     hipError_t e = hipModuleLaunchKernel(st.soft_fn[dtype], blocks, 1, 1, 64 * MASK_WPB, 1, 1, 0, (hipStream_t)stream,
+                                         args, nullptr);
+    return e == hipSuccess ? 0 : -EIO;
+}
+
+// ---- polar_sc_decode_to_info / polar_sc_decode_soft_to_info on per-mask plans: the kernel with the
+// information-bit epilogue (Gen::info_epilogue), one code object per input (POLAR_SC_F32 / F16 /
+// BF16 / I8), compiled on the first use of that input and cached under the key of its own source --
+std::string info_source(const polar_sc_plan &p, int input)
+{
+    return Gen(p.ops, p.lg).run_mask(p, input == POLAR_SC_I8 ? -1 : input, true);
+}
+
+const char *info_kernel_name(int input)
+{
+    return input == POLAR_SC_I8 ? "polar_sc_mask_info_kernel" : "polar_sc_mask_soft_info_kernel";
+}
+
+// Which inputs the one-launch kernel serves. The rule is kSoftFuse's: an input
+// whose decode_to_info is slower than its decode followed by polar_sc_extract_info, by more than
+// the spread of that pair's rounds at 65,536 x FB_N1024_K512, takes the two launches.
+constexpr bool kInfoFuse[4] = {true, true, true, true};   // POLAR_SC_F32, F16, BF16, I8
+
+// p.info_regs[input]: registers per lane of the kernel; 0 when this plan and input decode into the
+// workspace and extract with a second launch (not a per-mask plan, no information bit, the rule
+// above, or an object whose waves do not fit MASK_WPB per block). Under the plan lock.
+int info_compile(const polar_sc_plan &p, int input)
+{
+    if (p.info_regs[input] >= 0) return 0;
+    if (!p.jit || p.K == 0 || !kInfoFuse[input]) {
+        p.info_regs[input] = 0;
+        return 0;
+    }
+    std::string src;
+    try {
+        src = info_source(p, input);
+    } catch (const std::exception &e) {
+        p.jit_log = e.what();
+        return -ENOTSUP;
+    }
+    if (const int rc = rtc_compile(src, p.info_code[input], p.jit_log, true, nullptr, true)) return rc;
+    const int regs = kernel_regs(p.info_code[input], info_kernel_name(input));
+    if (regs < 0) return -EIO;
+    p.info_regs[input] = fit_waves(regs, MASK_WPB) == MASK_WPB ? regs : 0;
+    return 0;
+}
+
+int info_load(const polar_sc_plan &p, DevState &st, int input)
+{
+    if (st.info_fn[input]) return 0;
+    if (const int rc = info_compile(p, input)) {
+        std::fprintf(stderr, "polar_sc: information-bit kernel build failed (%d)%s%s\n", rc, p.jit_log.empty() ? "" : ":\n",
+                     p.jit_log.c_str());
+        return rc;
+    }
+    if (p.info_regs[input] == 0) return 0;   // two launches
+    if (hipError_t e = hipModuleLoadData(&st.info_module[input], p.info_code[input].data()); e != hipSuccess) {
+        std::fprintf(stderr, "polar_sc: hipModuleLoadData: %s\n", hipGetErrorString(e));
+        return -EIO;
+    }
+    if (hipModuleGetFunction(&st.info_fn[input], st.info_module[input], info_kernel_name(input)) != hipSuccess) return -EIO;
+    return 0;
+}
+
+// the launch shape of jit_launch; v: int8 LLRs (POLAR_SC_I8, the quantizer arguments unused) or
+// float channel values
+int info_launch(const DevState &st, int input, const void *v, float beta, int vsatn, int vsatp, uint64_t *info,
+                long batch, int info_stride, void *stream)
+{
+    const long waves = (batch + 7) / 8;
+    const unsigned blocks = (unsigned)((waves + MASK_WPB - 1) / MASK_WPB);
+    int b = (int)batch;
+    void *args[] = {(void *)&v, (void *)&info, (void *)&b, (void *)&info_stride, (void *)&beta, (void *)&vsatn,
+                    (void *)&vsatp};   // (the int8 kernel takes the first four)
+    hipError_t e = hipModuleLaunchKernel(st.info_fn[input], blocks, 1, 1, 64 * MASK_WPB, 1, 1, 0, (hipStream_t)stream,
                                          args, nullptr);
     return e == hipSuccess ? 0 : -EIO;
 }

@@ -37,6 +37,11 @@ struct DevState {
     // F16 / BF16), loaded by the first soft decode of that type on this device
     hipModule_t soft_module[3] = {nullptr, nullptr, nullptr};
     hipFunction_t soft_fn[3] = {nullptr, nullptr, nullptr};
+    // polar_sc_decode_to_info / polar_sc_decode_soft_to_info on per-mask plans: the kernel with the
+    // information-bit epilogue per input (POLAR_SC_F32 / F16 / BF16 / I8), loaded by the first such
+    // call of that input on this device
+    hipModule_t info_module[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipFunction_t info_fn[4] = {nullptr, nullptr, nullptr, nullptr};
     int simds = 0;                // SIMDs of the device (4 per CU), for launch sizing
     // registers per lane (VGPR + AGPR allocation, kernel descriptor) of the generated decode
     // kernel and of the pair segment kernel: the launch shape is capped so that a block's
@@ -185,6 +190,10 @@ struct polar_sc_plan {
     // (-1: not built yet; 0: this plan and type decode with two launches)
     mutable std::vector<char> soft_code[3];
     mutable int soft_regs[3] = {-1, -1, -1};
+    // polar_sc_decode_to_info / _soft_to_info: the same per input (index POLAR_SC_I8 = int8 LLRs);
+    // 0: decode into the workspace, then polar_sc_extract_info
+    mutable std::vector<char> info_code[4];
+    mutable int info_regs[4] = {-1, -1, -1, -1};
     mutable std::string jit_log;
 };
 
@@ -220,4 +229,12 @@ int soft_compile(const polar_sc_plan &p, int dtype);   // fills p.soft_code / p.
 int soft_load(const polar_sc_plan &p, DevState &st, int dtype);
 int soft_launch(const DevState &st, int dtype, const void *v, float beta, int vsatn, int vsatp, uint16_t *out,
                 long batch, int out_stride, void *stream);
+// polar_sc_decode_to_info / polar_sc_decode_soft_to_info on per-mask plans (polar_sc_jit.cpp): the
+// kernel with the information-bit epilogue of one input (POLAR_SC_F32 / F16 / BF16 / I8)
+std::string info_source(const polar_sc_plan &p, int input);
+const char *info_kernel_name(int input);
+int info_compile(const polar_sc_plan &p, int input);   // fills p.info_code / p.info_regs (host only, idempotent)
+int info_load(const polar_sc_plan &p, DevState &st, int input);
+int info_launch(const DevState &st, int input, const void *v, float beta, int vsatn, int vsatp, uint64_t *info,
+                long batch, int info_stride, void *stream);
 }  // namespace polar_host
