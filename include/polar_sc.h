@@ -387,6 +387,29 @@ int polar_sc_decode_soft_to_info(const polar_sc_plan *plan, const void *v_dev, i
                                  int vsatn, int vsatp, void *workspace, uint64_t *info_dev,
                                  size_t batch, void *stream);
 
+/* ---- Successive-cancellation list decoding, N <= 1024 ----
+ * int8 LLRs llr_dev[batch][N] (used by value; -128 is magnitude 128) -> the information words of
+ * polar_sc_extract_info ([batch][ceil(K/64)] uint64, every word written), decoded by a list
+ * decoder that keeps the list_size best paths (1, 2, 4 or 8) in the integer arithmetic DESIGN.md
+ * 3.11 defines: F = sign sign min, G clamped at +-32767, a u32 path metric, ties broken by
+ * (rank, bit). Only the plan's mask and N take part: its format fields (sigmag, extended, par,
+ * pruning) do not, and list_size = 1 is successive cancellation in THIS arithmetic, not bit-equal
+ * to polar_sc_decode (whose datapath clamps G at 2^(llr_bits-2) - 1 and carries -0).
+ *   crc_len = 0 (then crc_poly must be 0): the result is the best path (rank 0).
+ *   1 <= crc_len <= 32, crc_len < K: the last crc_len information bits are a CRC of the K - crc_len
+ *   before them (polynomial crc_poly with an implicit top bit, register zero, no reflection, no
+ *   final XOR, both MSB first); the result is the lowest rank whose bits pass, or rank 0.
+ *   rank_dev: NULL, or [batch] bytes: the rank chosen, 0xFF when a CRC was given and no path passed.
+ * One launch of a hipcc-built kernel (one wave per frame, all state in LDS). The first call on a
+ * device uploads the plan's mask table synchronously (polar_sc_plan_prepare does too); later calls
+ * allocate nothing and can be captured in a graph. Calls on different streams may overlap.
+ * Asynchronous on `stream`. -EINVAL: list_size, crc_len or crc_poly out of range, llr_dev not
+ * 4-byte aligned; -ENOTSUP: N > 1024 or an LLR_BITS 9 plan. batch == 0 returns 0, K == 0 launches
+ * nothing; batch <= 2^31 - 8. */
+int polar_sc_decode_list_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int list_size,
+                                 uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
+                                 void *stream);
+
 int polar_sc_plan_get_stats(const polar_sc_plan *plan, polar_sc_plan_stats *stats);
 
 /* Copy the compiled schedule (at most cap ops) and its length. */

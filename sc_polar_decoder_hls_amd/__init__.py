@@ -23,7 +23,7 @@ from . import _build
 __all__ = [
     "Decoder", "PolarError", "load_frozen_tab", "load_mask_file", "unpack_bits", "pack_bits",
     "default_config", "make_tuning", "lib", "selftest_lanes", "OPS", "build", "csim_sigma", "csim_states", "csim_frames",
-    "count_errors", "quantize", "SOFT_DTYPES",
+    "count_errors", "quantize", "SOFT_DTYPES", "crc_attach", "crc_bits",
 ]
 
 build = _build.build
@@ -131,6 +131,7 @@ EXPORTS = (
     "polar_sc_extract_info", "polar_sc_encode", "polar_sc_decode_info", "polar_info_to_codeword",
     "polar_sc_quantize", "polar_sc_soft_info_get", "polar_sc_decode_soft",
     "polar_sc_to_info_get", "polar_sc_decode_to_info", "polar_sc_decode_soft_to_info",
+    "polar_sc_decode_list_to_info",
 )
 
 _lib = None
@@ -176,6 +177,8 @@ def lib():
         "polar_sc_to_info_get": [p, i32, sz, p],
         "polar_sc_decode_to_info": [p, p, p, p, sz, p],
         "polar_sc_decode_soft_to_info": [p, p, i32, i32, i32, i32, p, p, sz, p],
+        "polar_sc_decode_list_to_info": [p, p, sz, i32, u32, i32, p, p, p],
+        "polar_sc_list_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
         "polar_sc_selftest_lanes": [p],
@@ -198,7 +201,7 @@ def lib():
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
-        f.restype = ctypes.c_char_p if name == "polar_sc_strerror" else i32
+        f.restype = ctypes.c_char_p if name == "polar_sc_strerror" else None if name == "polar_sc_list_shape" else i32
     _lib = L
     return L
 
@@ -640,6 +643,33 @@ class Decoder:
                     self._plan, ctypes.c_void_p(x.data_ptr()), inp, int(beta), vsatn, vsatp, ws, *ptrs))
         return out
 
+    # -- list decoding ------------------------------------------------------------
+    def decode_list(self, llr, list_size, crc=None, out=None, rank=None, stream=None):
+        """Successive-cancellation list decoding of int8 LLRs [B, N] (N <= 1024) with `list_size`
+        paths (1, 2, 4 or 8): returns (info, rank), the information words [B, info_words] of the
+        chosen path (int64, the rows of extract_info) and the rank chosen per frame (uint8 [B]).
+        crc: None (the best path, rank 0) or (poly, length): the last `length` information bits are
+        the CRC crc_attach() appends; the lowest rank that passes is chosen, rank 0 and 255 in
+        `rank` when none does. list_size = 1 is successive cancellation in the list decoder's own
+        arithmetic (G clamped at +-32767), not bit-equal to decode(). Asynchronous on `stream`."""
+        torch = self._check_llr(llr)
+        B = llr.shape[0]
+        poly, length = (0, 0) if crc is None else (int(crc[0]), int(crc[1]))
+        if out is None:
+            out = torch.empty((B, self.info_words), dtype=torch.int64, device=llr.device)
+        else:
+            self._check_out(out, llr, (B, self.info_words), torch.int64)
+        if rank is None:
+            rank = torch.zeros((B,), dtype=torch.uint8, device=llr.device)
+        else:
+            self._check_out(rank, llr, (B,), torch.uint8)
+        with torch.cuda.device(llr.device):
+            s = stream if stream is not None else torch.cuda.current_stream(llr.device)
+            _check("polar_sc_decode_list_to_info", lib().polar_sc_decode_list_to_info(
+                self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), poly, length,
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
+        return out, rank
+
     # -- information bits on the device (DESIGN.md 3.8) ----------------------------------------
     def _xform(self, fn, src, cols_in, cols_out, out, stream, name):
         torch = _torch()
@@ -694,6 +724,39 @@ class Decoder:
                 self._plan, ctypes.c_void_p(llr.data_ptr()), ctypes.c_void_p(xhat.data_ptr()),
                 ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(s.cuda_stream)))
         return out
+
+
+def crc_bits(bits, poly, length):
+    """CRC of the list decoder's rule over a 0/1 sequence, first bit first: polynomial `poly` with
+    an implicit top bit, `length` bits, register zero, no reflection, no final XOR. Returns the
+    `length` check bits, most significant first."""
+    top, keep, reg = 1 << (length - 1), (1 << length) - 1, 0
+    for b in bits:
+        fb = (1 if reg & top else 0) ^ int(b)
+        reg = ((reg << 1) & keep) ^ (poly if fb else 0)
+    return [(reg >> (length - 1 - m)) & 1 for m in range(length)]
+
+
+def crc_attach(payload_words, K, poly, length):
+    """Transmit side of decode_list(crc=(poly, length)), on the host: payload_words [B, ceil((K -
+    length) / 64)] uint64 rows whose bits 0 .. K - length - 1 are the message (higher bits ignored)
+    -> information words [B, ceil(K / 64)] uint64 with the CRC in bits K - length .. K - 1, ready
+    for encode()."""
+    if not (1 <= length <= 32 and length < K and 0 <= poly < (1 << length)):
+        raise ValueError("crc_attach: need 1 <= length <= 32, length < K and poly < 2^length")
+    msg = unpack_bits(np.atleast_2d(np.asarray(payload_words)), K - length)
+    out = np.zeros((msg.shape[0], K), dtype=np.uint8)
+    out[:, :K - length] = msg
+    for row in out:
+        row[K - length:] = crc_bits(row[:K - length], poly, length)
+    return pack_bits(out)
+
+
+def list_shape(N, list_size):
+    """(LDS bytes per wave, waves per block) of the list decoder's kernel for (N, list_size)."""
+    lds, wpb = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().polar_sc_list_shape(int(N), int(list_size), ctypes.byref(lds), ctypes.byref(wpb))
+    return lds.value, wpb.value
 
 
 def _soft_dtype(dtype):

@@ -32,6 +32,10 @@ extern "C" void polar_sc_xform_table(const uint8_t *mask, uint32_t N, uint32_t *
 extern "C" int polar_sc_launch_xform(int encode, const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev,
                                      uint32_t N, uint32_t K, size_t batch, void *stream);
 extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stream);
+// polar_sc_list.hip: the list decoder of N <= 1024 (reads the same mask table)
+extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
+                                    int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
+                                    void *stream);
 // polar_sc_soft.hip: the stand-alone quantizer (0 or a hipError_t; arguments checked here)
 extern "C" int polar_sc_launch_quantize(const void *v_dev, int dtype, size_t n, int beta, int vsatn, int vsatp,
                                         void *q_dev, int bits, void *stream);
@@ -1371,6 +1375,25 @@ int polar_sc_decode_soft_to_info(const polar_sc_plan *p, const void *v_dev, int 
     if (!p || !quant_args_ok(dtype, beta, vsatn, vsatp, soft_bits(p))) return -EINVAL;
     if (batch > 0 && v_dev && !elem_aligned(v_dev, dtype)) return -EINVAL;
     return to_info_common(p, v_dev, dtype, beta, vsatn, vsatp, workspace, info_dev, batch, stream);
+}
+
+int polar_sc_decode_list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                 uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
+{
+    if (!p) return -EINVAL;
+    if (list_size != 1 && list_size != 2 && list_size != 4 && list_size != 8) return -EINVAL;
+    if (crc_len < 0 || crc_len > 32 || (crc_len == 0 && crc_poly != 0)) return -EINVAL;
+    if (crc_len > 0 && crc_len < 32 && (crc_poly >> crc_len) != 0) return -EINVAL;
+    if (crc_len > 0 && (uint32_t)crc_len >= p->K) return -EINVAL;
+    if (p->N > 1024u || p->cfg.llr_bits > 8) return -ENOTSUP;
+    if (batch == 0 || p->K == 0) return 0;
+    if (!llr_dev || !info_dev || ((uintptr_t)llr_dev & 3u) || ((uintptr_t)info_dev & 7u)) return -EINVAL;
+    if (batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    const void *tab = nullptr;
+    if (const int e = ensure_xform(p, &tab)) return e;
+    const int rc = polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
+                                        info_dev, rank_dev, stream);
+    return rc ? hip_fail("list decode launch", (hipError_t)rc) : 0;
 }
 
 int polar_sc_decode(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *hard_bits_dev,
