@@ -410,6 +410,42 @@ int polar_sc_decode_list_to_info(const polar_sc_plan *plan, const int8_t *llr_de
                                  uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
                                  void *stream);
 
+/* ---- Adaptive CRC-aided decoding, N <= 1024 ----
+ * Successive cancellation first, the list decoder only for the frames whose SC result fails the
+ * CRC, in one asynchronous call with no host round trip. The CRC is that of
+ * polar_sc_decode_list_to_info and is mandatory here: 1 <= crc_len <= 32, crc_len < K, crc_poly <
+ * 2^crc_len. A row of information words passes when the remainder of all its K bits (bit 0 first,
+ * register zero, no final XOR) is zero, which is the same as its last crc_len bits being the CRC of
+ * the K - crc_len before them. -EINVAL: arguments out of range; -ENOTSUP: N > 1024 or LLR_BITS 9. */
+
+/* pass_dev[f] = 1 when row f of info_dev ([batch][ceil(K/64)] uint64; bits at and above K are
+ * ignored) passes, else 0. One launch (one lane per row, the CRC as c parity masks). The first call
+ * with a new (crc_poly, crc_len) on a device uploads the masks synchronously; later calls allocate
+ * nothing and can be captured in a graph. Asynchronous on `stream`; batch == 0 returns 0. */
+int polar_sc_crc_check(const polar_sc_plan *plan, const uint64_t *info_dev, size_t batch, uint32_t crc_poly,
+                       int crc_len, uint8_t *pass_dev, void *stream);
+
+/* *bytes = the workspace polar_sc_decode_adaptive_to_info needs for `batch` frames: the list of
+ * failing frames (batch uint32, rounded up to 16 bytes), their count (16 bytes), and the workspace
+ * of polar_sc_decode_to_info (0 on the plans served). Host only; compiles the one-launch kernel of
+ * polar_sc_decode_to_info if needed. -ENOTSUP: a plan without that kernel or without list decoding. */
+int polar_sc_adaptive_workspace(const polar_sc_plan *plan, size_t batch, size_t *bytes);
+
+/* Per frame f: sc = the row polar_sc_decode_to_info gives (the plan's datapath: the LLR is the low
+ * llr_bits of the byte). If sc passes the CRC: info_dev[f] = sc, rank 0, stage 0. Otherwise info_dev[f]
+ * and rank are exactly what polar_sc_decode_list_to_info(list_size, crc) gives for the frame (the byte
+ * by value; rank 0xFF and the best path when no path passes), stage 1. The two stages see the same
+ * LLRs while |llr| <= 2^(llr_bits-1) - 1, which is the caller's business.
+ *   workspace: polar_sc_adaptive_workspace bytes, 16-byte aligned, contents unspecified afterwards
+ *   rank_dev, stage_dev: NULL, or [batch] bytes
+ * On `stream`: the SC kernel, a kernel that zeroes the count, the check, the list kernel over the
+ * listed frames (kernels only, no memset node). The first call on a device loads the SC kernel and
+ * uploads the tables synchronously; later calls allocate nothing, read nothing back and can be
+ * captured in a graph. llr_dev 4-byte aligned; batch == 0 returns 0; batch <= 2^31 - 8. */
+int polar_sc_decode_adaptive_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int list_size,
+                                     uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev,
+                                     uint8_t *rank_dev, uint8_t *stage_dev, void *stream);
+
 int polar_sc_plan_get_stats(const polar_sc_plan *plan, polar_sc_plan_stats *stats);
 
 /* Copy the compiled schedule (at most cap ops) and its length. */

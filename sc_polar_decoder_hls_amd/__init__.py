@@ -132,6 +132,7 @@ EXPORTS = (
     "polar_sc_quantize", "polar_sc_soft_info_get", "polar_sc_decode_soft",
     "polar_sc_to_info_get", "polar_sc_decode_to_info", "polar_sc_decode_soft_to_info",
     "polar_sc_decode_list_to_info",
+    "polar_sc_crc_check", "polar_sc_adaptive_workspace", "polar_sc_decode_adaptive_to_info",
 )
 
 _lib = None
@@ -178,6 +179,9 @@ def lib():
         "polar_sc_decode_to_info": [p, p, p, p, sz, p],
         "polar_sc_decode_soft_to_info": [p, p, i32, i32, i32, i32, p, p, sz, p],
         "polar_sc_decode_list_to_info": [p, p, sz, i32, u32, i32, p, p, p],
+        "polar_sc_crc_check": [p, p, sz, u32, i32, p, p],
+        "polar_sc_adaptive_workspace": [p, sz, ctypes.POINTER(sz)],
+        "polar_sc_decode_adaptive_to_info": [p, p, sz, i32, u32, i32, p, p, p, p, p],
         "polar_sc_list_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
@@ -669,6 +673,73 @@ class Decoder:
                 self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), poly, length,
                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
         return out, rank
+
+    # -- adaptive CRC-aided decoding -----------------------------------------------
+    def crc_check(self, info, crc, out=None, stream=None):
+        """Which rows of information words (torch.int64 CUDA [B, info_words], as decode_to_info and
+        decode_list return) pass the CRC crc = (poly, length) of decode_list: a uint8 [B] tensor,
+        1 = passes. Bits of a row at and above K are ignored. Asynchronous on `stream`."""
+        torch = _torch()
+        if not (isinstance(info, torch.Tensor) and info.is_cuda and info.dtype == torch.int64):
+            raise TypeError("info must be a CUDA int64 tensor")
+        if info.dim() != 2 or info.shape[1] != self.info_words or not info.is_contiguous():
+            raise ValueError("info must be contiguous [B, %d]" % self.info_words)
+        B = info.shape[0]
+        if out is None:
+            out = torch.empty((B,), dtype=torch.uint8, device=info.device)
+        else:
+            self._check_out(out, info, (B,), torch.uint8)
+        with torch.cuda.device(info.device):
+            s = stream if stream is not None else torch.cuda.current_stream(info.device)
+            _check("polar_sc_crc_check", lib().polar_sc_crc_check(
+                self._plan, ctypes.c_void_p(info.data_ptr()), B, int(crc[0]), int(crc[1]),
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    def adaptive_workspace(self, batch):
+        """Bytes of workspace decode_adaptive() of `batch` frames needs. Host only."""
+        n = ctypes.c_size_t(0)
+        _check("polar_sc_adaptive_workspace", lib().polar_sc_adaptive_workspace(self._plan, int(batch), ctypes.byref(n)))
+        return n.value
+
+    def decode_adaptive(self, llr, list_size, crc, out=None, rank=None, stage=None, workspace=None, stream=None):
+        """Adaptive CRC-aided decoding of int8 LLRs [B, N] (N <= 1024): decode_to_info first, and
+        decode_list(list_size, crc) only for the frames whose result fails crc = (poly, length), all
+        on the device in one asynchronous call. Returns (info, rank, stage): the information words
+        [B, info_words] (int64), and per frame (uint8 [B]) the rank (0 where successive cancellation
+        passed, else what decode_list gives) and the stage that decided it (0 = successive
+        cancellation, 1 = the list decoder). The two stages read the same LLRs while |llr| <=
+        2^(llr_bits-1) - 1. workspace: a uint8 CUDA tensor of adaptive_workspace(B) bytes, 16-byte
+        aligned, allocated here when not given."""
+        torch = self._check_llr(llr)
+        B = llr.shape[0]
+        if out is None:
+            out = torch.empty((B, self.info_words), dtype=torch.int64, device=llr.device)
+        else:
+            self._check_out(out, llr, (B, self.info_words), torch.int64)
+        if rank is None:
+            rank = torch.zeros((B,), dtype=torch.uint8, device=llr.device)
+        else:
+            self._check_out(rank, llr, (B,), torch.uint8)
+        if stage is None:
+            stage = torch.zeros((B,), dtype=torch.uint8, device=llr.device)
+        else:
+            self._check_out(stage, llr, (B,), torch.uint8)
+        need = self.adaptive_workspace(B)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=llr.device)
+        if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.is_contiguous()
+                and workspace.device == llr.device):
+            raise ValueError("workspace must be a contiguous CUDA tensor on the device of llr")
+        if workspace.numel() * workspace.element_size() < need:
+            raise ValueError("workspace must hold %d bytes" % need)
+        with torch.cuda.device(llr.device):
+            s = stream if stream is not None else torch.cuda.current_stream(llr.device)
+            _check("polar_sc_decode_adaptive_to_info", lib().polar_sc_decode_adaptive_to_info(
+                self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), int(crc[0]), int(crc[1]),
+                ctypes.c_void_p(workspace.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(stage.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
+        return out, rank, stage
 
     # -- information bits on the device (DESIGN.md 3.8) ----------------------------------------
     def _xform(self, fn, src, cols_in, cols_out, out, stream, name):

@@ -33,6 +33,15 @@ extern "C" int polar_sc_launch_xform(int encode, const void *tab_dev, const uint
                                      uint32_t N, uint32_t K, size_t batch, void *stream);
 extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stream);
 // polar_sc_list.hip: the list decoder of N <= 1024 (reads the same mask table)
+extern "C" int polar_sc_launch_list_indexed(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
+                                            uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
+                                            uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
+                                            void *stream);
+extern "C" size_t polar_sc_crc_table_dwords(uint32_t K, uint32_t c);
+extern "C" void polar_sc_crc_table(uint32_t K, uint32_t poly, uint32_t c, uint32_t *tab);
+extern "C" int polar_sc_launch_crc_check(const void *tab_dev, const uint64_t *info_dev, size_t batch, uint32_t K,
+                                         uint32_t c, uint8_t *flag_dev, uint32_t pass_value, uint8_t *zero_dev,
+                                         uint32_t *idx_dev, uint32_t *count_dev, void *stream);
 extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
                                     int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
                                     void *stream);
@@ -686,6 +695,34 @@ int ensure_xform(const polar_sc_plan *p, const void **tab)
     return 0;
 }
 
+// the CRC check's parity masks for (poly, len) on the current device (built and uploaded by the
+// first call that names them, under the plan lock; freed with the plan)
+int ensure_crc(const polar_sc_plan *p, uint32_t poly, uint32_t len, const void **tab)
+{
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return hip_fail("hipGetDevice", e);
+    std::lock_guard<std::mutex> lk(p->mu);
+    DevState &st = p->dev[dev];
+    for (const auto &ct : st.crc_tabs)
+        if (ct.poly == poly && ct.len == len) {
+            *tab = ct.dev;
+            return 0;
+        }
+    std::vector<uint32_t> h(polar_sc_crc_table_dwords(p->K, len));
+    polar_sc_crc_table(p->K, poly, len, h.data());
+    void *d = nullptr;
+    if (hipMalloc(&d, h.size() * 4u) != hipSuccess) return -ENOMEM;
+    if (hipError_t e = hipMemcpy(d, h.data(), h.size() * 4u, hipMemcpyHostToDevice); e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_fail("CRC table upload", e);
+    }
+    DevState::CrcTab ct;
+    ct.poly = poly, ct.len = len, ct.dev = d;
+    st.crc_tabs.push_back(ct);
+    *tab = d;
+    return 0;
+}
+
 // extraction (encode = 0: x^ rows -> information rows) / encoding (1: the reverse) of resident frames
 int xform_common(const polar_sc_plan *p, int encode, const uint64_t *in, uint64_t *out, size_t batch, void *stream)
 {
@@ -1206,6 +1243,7 @@ int polar_sc_plan_destroy(polar_sc_plan *p)
         if (kv.second.scratch) (void)hipFree(kv.second.scratch);
         if (kv.second.wide) (void)hipFree(kv.second.wide);
         if (kv.second.xtab) (void)hipFree(kv.second.xtab);
+        for (auto &ct : kv.second.crc_tabs) (void)hipFree(ct.dev);
     }
     if (have_dev && !p->dev.empty()) (void)hipSetDevice(cur);
     delete p;
@@ -1394,6 +1432,74 @@ int polar_sc_decode_list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, 
     const int rc = polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
                                         info_dev, rank_dev, stream);
     return rc ? hip_fail("list decode launch", (hipError_t)rc) : 0;
+}
+
+// ---- adaptive CRC-aided decoding (include/polar_sc.h) -----------------------------
+namespace {
+// the rules both calls share: a mandatory CRC as polar_sc_decode_list_to_info takes it, on a plan
+// the list decoder serves
+int crc_args(const polar_sc_plan *p, uint32_t crc_poly, int crc_len)
+{
+    if (crc_len < 1 || crc_len > 32 || (crc_len < 32 && (crc_poly >> crc_len) != 0)) return -EINVAL;
+    if ((uint32_t)crc_len >= p->K) return -EINVAL;
+    if (p->N > 1024u || p->cfg.llr_bits > 8) return -ENOTSUP;
+    return 0;
+}
+// the adaptive workspace: the index list, then the count in a 16-byte slot of its own
+size_t adaptive_count_offset(size_t batch) { return (batch * 4u + 15u) & ~(size_t)15u; }
+}  // namespace
+
+int polar_sc_crc_check(const polar_sc_plan *p, const uint64_t *info_dev, size_t batch, uint32_t crc_poly, int crc_len,
+                       uint8_t *pass_dev, void *stream)
+{
+    if (!p) return -EINVAL;
+    if (const int rc = crc_args(p, crc_poly, crc_len)) return rc;
+    if (batch == 0) return 0;
+    if (!info_dev || !pass_dev || ((uintptr_t)info_dev & 7u) || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    const void *h = nullptr;
+    if (const int e = ensure_crc(p, crc_poly, (uint32_t)crc_len, &h)) return e;
+    const int rc = polar_sc_launch_crc_check(h, info_dev, batch, p->K, (uint32_t)crc_len, pass_dev, 1u, nullptr, nullptr,
+                                             nullptr, stream);
+    return rc ? hip_fail("CRC check launch", (hipError_t)rc) : 0;
+}
+
+int polar_sc_adaptive_workspace(const polar_sc_plan *p, size_t batch, size_t *bytes)
+{
+    if (!p || !bytes || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    if (p->N > 1024u || p->cfg.llr_bits > 8) return -ENOTSUP;
+    polar_sc_to_info ti{};
+    if (const int rc = polar_sc_to_info_get(p, POLAR_SC_I8, batch, &ti)) return rc;
+    if (!ti.fused) return -ENOTSUP;
+    *bytes = adaptive_count_offset(batch) + 16u + (size_t)ti.workspace_bytes;
+    return 0;
+}
+
+int polar_sc_decode_adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                     uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev,
+                                     uint8_t *rank_dev, uint8_t *stage_dev, void *stream)
+{
+    if (!p) return -EINVAL;
+    if (list_size != 1 && list_size != 2 && list_size != 4 && list_size != 8) return -EINVAL;
+    if (const int rc = crc_args(p, crc_poly, crc_len)) return rc;
+    if (batch == 0) return 0;
+    if (!llr_dev || !info_dev || ((uintptr_t)llr_dev & 3u) || ((uintptr_t)info_dev & 7u)) return -EINVAL;
+    if (!workspace || ((uintptr_t)workspace & 15u) || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    size_t need = 0;   // (host only: the one-launch SC kernel is compiled here if it was not)
+    if (const int rc = polar_sc_adaptive_workspace(p, batch, &need)) return rc;
+    const void *tab = nullptr, *h = nullptr;
+    if (const int e = ensure_xform(p, &tab)) return e;
+    if (const int e = ensure_crc(p, crc_poly, (uint32_t)crc_len, &h)) return e;
+    uint32_t *idx = (uint32_t *)workspace;
+    uint32_t *count = (uint32_t *)((char *)workspace + adaptive_count_offset(batch));
+    // SC into info_dev; the count zeroed, the rows checked, the failing ones listed (stage, rank 0);
+    // the list decoder over the listed frames
+    if (const int rc = to_info_common(p, llr_dev, POLAR_SC_I8, 1, 0, 0, nullptr, info_dev, batch, stream)) return rc;
+    int rc = polar_sc_launch_crc_check(h, info_dev, batch, p->K, (uint32_t)crc_len, stage_dev, 0u, rank_dev, idx, count,
+                                       stream);
+    if (rc) return hip_fail("CRC check launch", (hipError_t)rc);
+    rc = polar_sc_launch_list_indexed(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len, info_dev,
+                                      rank_dev, idx, count, stream);
+    return rc ? hip_fail("indexed list decode launch", (hipError_t)rc) : 0;
 }
 
 int polar_sc_decode(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *hard_bits_dev,

@@ -293,18 +293,30 @@ __device__ __forceinline__ bool crc_passes(const u32 *row, u32 K, u32 poly, u32 
     return bad == 0u;
 }
 
-template <int LOGN, int L>
+// INDEXED = false: the direct launch, wave slot f decodes frame f of the batch (idx and count unused).
+// INDEXED = true: the indexed launch of adaptive decoding: the frames to decode are
+// idx[0 .. *idx_count), a list only the device knows (polar_sc_adaptive.hip wrote it earlier on the
+// stream). The grid still has a wave slot per frame of the batch; slot s decodes frame idx[s], and a
+// slot at or past the count returns before any other load. An entry outside the batch is skipped, so
+// that nothing a wrong list holds can be used as an address.
+template <int LOGN, int L, bool INDEXED>
 __global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_kernel(
     const Ent *__restrict__ tab, const int8_t *__restrict__ llr, u32 batch, u32 K, u32 poly, u32 clen,
-    u32 *__restrict__ info, uint8_t *__restrict__ rank_out)
+    u32 *__restrict__ info, uint8_t *__restrict__ rank_out, const u32 *__restrict__ idx,
+    const u32 *__restrict__ idx_count)
 {
     typedef Shape<LOGN, L> S;
     constexpr int N = S::N;
     __shared__ u32 lds[S::WPB * S::WAVE_DW];
     const u32 lane = threadIdx.x & 63u;
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const size_t frame = (size_t)blockIdx.x * S::WPB + wave;
+    size_t frame = (size_t)blockIdx.x * S::WPB + wave;
     if (frame >= batch) return;                      // (wave-uniform; no block-wide barrier anywhere)
+    if constexpr (INDEXED) {
+        if (frame >= *idx_count) return;
+        frame = (size_t)__builtin_amdgcn_readfirstlane(idx[frame]);
+        if (frame >= batch) return;
+    }
 
     Wave<LOGN, L> W;
     W.R = lds + wave * S::WAVE_DW;
@@ -380,25 +392,43 @@ __global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_kern
     if (rank_out && lane == 0u) rank_out[frame] = (uint8_t)((clen && !votes) ? 0xFFu : pick);
 }
 
+// idx == nullptr: the direct kernel over frames 0 .. batch - 1; else the indexed kernel
 template <int LOGN, int L>
 void launch(hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly, u32 clen, u32 *info,
-            uint8_t *rank_out)
+            uint8_t *rank_out, const u32 *idx, const u32 *count)
 {
     constexpr int WPB = Shape<LOGN, L>::WPB;
-    const unsigned blocks = (unsigned)(((size_t)batch + WPB - 1) / WPB);
-    hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L>), dim3(blocks), dim3(64 * WPB), 0, s, tab, llr, batch, K, poly,
-                       clen, info, rank_out);
+    const dim3 blocks((unsigned)(((size_t)batch + WPB - 1) / WPB)), threads(64 * WPB);
+    if (idx)
+        hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, true>), blocks, threads, 0, s, tab, llr, batch, K, poly, clen,
+                           info, rank_out, idx, count);
+    else
+        hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, false>), blocks, threads, 0, s, tab, llr, batch, K, poly, clen,
+                           info, rank_out, idx, count);
 }
 
 template <int LOGN>
 void launch_l(int L, hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly, u32 clen,
-              u32 *info, uint8_t *rank_out)
+              u32 *info, uint8_t *rank_out, const u32 *idx, const u32 *count)
 {
     switch (L) {
-    case 1: launch<LOGN, 1>(s, tab, llr, batch, K, poly, clen, info, rank_out); break;
-    case 2: launch<LOGN, 2>(s, tab, llr, batch, K, poly, clen, info, rank_out); break;
-    case 4: launch<LOGN, 4>(s, tab, llr, batch, K, poly, clen, info, rank_out); break;
-    default: launch<LOGN, 8>(s, tab, llr, batch, K, poly, clen, info, rank_out); break;
+    case 1: launch<LOGN, 1>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    case 2: launch<LOGN, 2>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    case 4: launch<LOGN, 4>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    default: launch<LOGN, 8>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    }
+}
+
+void launch_n(uint32_t N, int L, hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly,
+              u32 clen, u32 *info, uint8_t *rank_out, const u32 *idx, const u32 *count)
+{
+    switch (N) {
+    case 32: launch_l<5>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    case 64: launch_l<6>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    case 128: launch_l<7>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    case 256: launch_l<8>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    case 512: launch_l<9>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
+    default: launch_l<10>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
     }
 }
 
@@ -411,19 +441,20 @@ extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, 
                                     int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
                                     void *stream)
 {
-    using namespace polar_list;
-    const Ent *tab = (const Ent *)tab_dev;
-    hipStream_t s = (hipStream_t)stream;
-    u32 *info = (u32 *)info_dev;
-    const u32 b = (u32)batch;
-    switch (N) {
-    case 32: launch_l<5>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev); break;
-    case 64: launch_l<6>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev); break;
-    case 128: launch_l<7>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev); break;
-    case 256: launch_l<8>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev); break;
-    case 512: launch_l<9>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev); break;
-    default: launch_l<10>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev); break;
-    }
+    polar_list::launch_n(N, L, (hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly,
+                         clen, (uint32_t *)info_dev, rank_dev, nullptr, nullptr);
+    return (int)hipGetLastError();
+}
+
+// The same decoder over the frames idx_dev[0 .. *count_dev) only (both written earlier on `stream`;
+// idx_dev holds `batch` entries): info_dev and rank_dev rows of the other frames are left alone.
+extern "C" int polar_sc_launch_list_indexed(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
+                                            uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
+                                            uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
+                                            void *stream)
+{
+    polar_list::launch_n(N, L, (hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly,
+                         clen, (uint32_t *)info_dev, rank_dev, idx_dev, count_dev);
     return (int)hipGetLastError();
 }
 

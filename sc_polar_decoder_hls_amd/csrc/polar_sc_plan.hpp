@@ -33,6 +33,12 @@ struct DevState {
     hipFunction_t fn16 = nullptr;
     void *ops16 = nullptr;              //   and its schedule when it differs from `ops`
     void *xtab = nullptr;               // per-dword mask table of the transform kernels (polar_sc_xform.hip)
+    // parity masks of the CRC check (polar_sc_adaptive.hip) per (poly, length) seen on this device
+    struct CrcTab {
+        uint32_t poly = 0, len = 0;
+        void *dev = nullptr;
+    };
+    std::vector<CrcTab> crc_tabs;
     // polar_sc_decode_soft on per-mask plans: the fused kernel per input type (POLAR_SC_F32 /
     // F16 / BF16), loaded by the first soft decode of that type on this device
     hipModule_t soft_module[3] = {nullptr, nullptr, nullptr};
