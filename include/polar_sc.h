@@ -405,10 +405,24 @@ int polar_sc_decode_soft_to_info(const polar_sc_plan *plan, const void *v_dev, i
  * allocate nothing and can be captured in a graph. Calls on different streams may overlap.
  * Asynchronous on `stream`. -EINVAL: list_size, crc_len or crc_poly out of range, llr_dev not
  * 4-byte aligned; -ENOTSUP: N > 1024 or an LLR_BITS 9 plan. batch == 0 returns 0, K == 0 launches
- * nothing; batch <= 2^31 - 8. */
+ * nothing; batch <= 2^31 - 8.
+ * This is the entry for list_size <= 8, kept for compatibility: it refuses 16 and 32 (-EINVAL).
+ * polar_sc_decode_list_wide_to_info below takes every size. */
 int polar_sc_decode_list_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int list_size,
                                  uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
                                  void *stream);
+
+/* The same call for list_size in {1, 2, 4, 8, 16, 32}: arguments, results, rule and error codes are
+ * those of polar_sc_decode_list_to_info (rank_dev holds 0 .. list_size - 1, or 0xFF). list_size <= 8
+ * is that call unchanged; 16 and 32 launch the wide-list kernel (one wave per frame, 5-bit index
+ * fields, the top LLR level computed from the channel instead of stored: DESIGN.md 3.11). */
+int polar_sc_decode_list_wide_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int list_size,
+                                      uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
+                                      void *stream);
+
+/* Static LDS per wave (bytes) and waves per block of the wide-list kernel for N = 32 .. 1024 (a
+ * power of two) and list_size 16 or 32; zeros for anything else. Host only. */
+void polar_sc_list_wide_shape(uint32_t N, int list_size, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block);
 
 /* ---- Adaptive CRC-aided decoding, N <= 1024 ----
  * Successive cancellation first, the list decoder only for the frames whose SC result fails the
@@ -445,6 +459,14 @@ int polar_sc_adaptive_workspace(const polar_sc_plan *plan, size_t batch, size_t 
 int polar_sc_decode_adaptive_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int list_size,
                                      uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev,
                                      uint8_t *rank_dev, uint8_t *stage_dev, void *stream);
+
+/* polar_sc_decode_adaptive_to_info above is the entry for list_size <= 8, kept for compatibility (it
+ * refuses 16 and 32 with -EINVAL). This one takes list_size in {1, 2, 4, 8, 16, 32} with the same
+ * arguments, workspace (which does not depend on list_size), results and error codes; the failing
+ * frames then get what polar_sc_decode_list_wide_to_info(list_size, crc) gives. */
+int polar_sc_decode_adaptive_wide_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch,
+                                          int list_size, uint32_t crc_poly, int crc_len, void *workspace,
+                                          uint64_t *info_dev, uint8_t *rank_dev, uint8_t *stage_dev, void *stream);
 
 int polar_sc_plan_get_stats(const polar_sc_plan *plan, polar_sc_plan_stats *stats);
 

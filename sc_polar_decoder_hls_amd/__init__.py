@@ -131,8 +131,9 @@ EXPORTS = (
     "polar_sc_extract_info", "polar_sc_encode", "polar_sc_decode_info", "polar_info_to_codeword",
     "polar_sc_quantize", "polar_sc_soft_info_get", "polar_sc_decode_soft",
     "polar_sc_to_info_get", "polar_sc_decode_to_info", "polar_sc_decode_soft_to_info",
-    "polar_sc_decode_list_to_info",
+    "polar_sc_decode_list_to_info", "polar_sc_decode_list_wide_to_info",
     "polar_sc_crc_check", "polar_sc_adaptive_workspace", "polar_sc_decode_adaptive_to_info",
+    "polar_sc_decode_adaptive_wide_to_info",
 )
 
 _lib = None
@@ -183,6 +184,9 @@ def lib():
         "polar_sc_adaptive_workspace": [p, sz, ctypes.POINTER(sz)],
         "polar_sc_decode_adaptive_to_info": [p, p, sz, i32, u32, i32, p, p, p, p, p],
         "polar_sc_list_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
+        "polar_sc_decode_list_wide_to_info": [p, p, sz, i32, u32, i32, p, p, p],
+        "polar_sc_decode_adaptive_wide_to_info": [p, p, sz, i32, u32, i32, p, p, p, p, p],
+        "polar_sc_list_wide_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
         "polar_sc_selftest_lanes": [p],
@@ -205,7 +209,7 @@ def lib():
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
-        f.restype = ctypes.c_char_p if name == "polar_sc_strerror" else None if name == "polar_sc_list_shape" else i32
+        f.restype = ctypes.c_char_p if name == "polar_sc_strerror" else None if name.endswith("_shape") else i32
     _lib = L
     return L
 
@@ -650,8 +654,9 @@ class Decoder:
     # -- list decoding ------------------------------------------------------------
     def decode_list(self, llr, list_size, crc=None, out=None, rank=None, stream=None):
         """Successive-cancellation list decoding of int8 LLRs [B, N] (N <= 1024) with `list_size`
-        paths (1, 2, 4 or 8): returns (info, rank), the information words [B, info_words] of the
-        chosen path (int64, the rows of extract_info) and the rank chosen per frame (uint8 [B]).
+        paths (1, 2, 4, 8, 16 or 32; 16 and 32 run the wide-list kernel, through
+        polar_sc_decode_list_wide_to_info): returns (info, rank), the information words [B, info_words] of
+        the chosen path (int64, the rows of extract_info) and the rank chosen per frame (uint8 [B]).
         crc: None (the best path, rank 0) or (poly, length): the last `length` information bits are
         the CRC crc_attach() appends; the lowest rank that passes is chosen, rank 0 and 255 in
         `rank` when none does. list_size = 1 is successive cancellation in the list decoder's own
@@ -669,7 +674,8 @@ class Decoder:
             self._check_out(rank, llr, (B,), torch.uint8)
         with torch.cuda.device(llr.device):
             s = stream if stream is not None else torch.cuda.current_stream(llr.device)
-            _check("polar_sc_decode_list_to_info", lib().polar_sc_decode_list_to_info(
+            fn = "polar_sc_decode_list_wide_to_info" if int(list_size) in (16, 32) else "polar_sc_decode_list_to_info"
+            _check(fn, getattr(lib(), fn)(
                 self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), poly, length,
                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
         return out, rank
@@ -705,7 +711,8 @@ class Decoder:
     def decode_adaptive(self, llr, list_size, crc, out=None, rank=None, stage=None, workspace=None, stream=None):
         """Adaptive CRC-aided decoding of int8 LLRs [B, N] (N <= 1024): decode_to_info first, and
         decode_list(list_size, crc) only for the frames whose result fails crc = (poly, length), all
-        on the device in one asynchronous call. Returns (info, rank, stage): the information words
+        on the device in one asynchronous call; list_size 1 .. 32 as decode_list takes it, and the
+        workspace does not depend on it. Returns (info, rank, stage): the information words
         [B, info_words] (int64), and per frame (uint8 [B]) the rank (0 where successive cancellation
         passed, else what decode_list gives) and the stage that decided it (0 = successive
         cancellation, 1 = the list decoder). The two stages read the same LLRs while |llr| <=
@@ -735,7 +742,9 @@ class Decoder:
             raise ValueError("workspace must hold %d bytes" % need)
         with torch.cuda.device(llr.device):
             s = stream if stream is not None else torch.cuda.current_stream(llr.device)
-            _check("polar_sc_decode_adaptive_to_info", lib().polar_sc_decode_adaptive_to_info(
+            fn = "polar_sc_decode_adaptive_wide_to_info" if int(list_size) in (16, 32) else \
+                "polar_sc_decode_adaptive_to_info"
+            _check(fn, getattr(lib(), fn)(
                 self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), int(crc[0]), int(crc[1]),
                 ctypes.c_void_p(workspace.data_ptr()), ctypes.c_void_p(out.data_ptr()),
                 ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(stage.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
@@ -824,9 +833,11 @@ def crc_attach(payload_words, K, poly, length):
 
 
 def list_shape(N, list_size):
-    """(LDS bytes per wave, waves per block) of the list decoder's kernel for (N, list_size)."""
+    """(LDS bytes per wave, waves per block) of the list decoder's kernel for (N, list_size): the
+    narrow kernel for list_size <= 8, the wide-list kernel for 16 and 32."""
     lds, wpb = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    lib().polar_sc_list_shape(int(N), int(list_size), ctypes.byref(lds), ctypes.byref(wpb))
+    fn = lib().polar_sc_list_wide_shape if int(list_size) in (16, 32) else lib().polar_sc_list_shape
+    fn(int(N), int(list_size), ctypes.byref(lds), ctypes.byref(wpb))
     return lds.value, wpb.value
 
 

@@ -45,6 +45,11 @@ extern "C" int polar_sc_launch_crc_check(const void *tab_dev, const uint64_t *in
 extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
                                     int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
                                     void *stream);
+// polar_sc_list_wide.hip: the same rule with 16 or 32 paths (idx_dev NULL: every frame of the batch)
+extern "C" int polar_sc_launch_list_wide(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
+                                         uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
+                                         uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
+                                         void *stream);
 // polar_sc_soft.hip: the stand-alone quantizer (0 or a hipError_t; arguments checked here)
 extern "C" int polar_sc_launch_quantize(const void *v_dev, int dtype, size_t n, int beta, int vsatn, int vsatp,
                                         void *q_dev, int bits, void *stream);
@@ -1415,11 +1420,13 @@ int polar_sc_decode_soft_to_info(const polar_sc_plan *p, const void *v_dev, int 
     return to_info_common(p, v_dev, dtype, beta, vsatn, vsatp, workspace, info_dev, batch, stream);
 }
 
-int polar_sc_decode_list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
-                                 uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
+namespace {
+// the one body of the list entries: max_list = 8 (the narrow kernel only) or 32
+int list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size, int max_list,
+                 uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
 {
     if (!p) return -EINVAL;
-    if (list_size != 1 && list_size != 2 && list_size != 4 && list_size != 8) return -EINVAL;
+    if (list_size < 1 || list_size > max_list || (list_size & (list_size - 1))) return -EINVAL;
     if (crc_len < 0 || crc_len > 32 || (crc_len == 0 && crc_poly != 0)) return -EINVAL;
     if (crc_len > 0 && crc_len < 32 && (crc_poly >> crc_len) != 0) return -EINVAL;
     if (crc_len > 0 && (uint32_t)crc_len >= p->K) return -EINVAL;
@@ -1429,9 +1436,26 @@ int polar_sc_decode_list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, 
     if (batch > (size_t)0x7FFFFFF8) return -EINVAL;
     const void *tab = nullptr;
     if (const int e = ensure_xform(p, &tab)) return e;
-    const int rc = polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
-                                        info_dev, rank_dev, stream);
+    const int rc = list_size > 8
+                       ? polar_sc_launch_list_wide(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly,
+                                                   (uint32_t)crc_len, info_dev, rank_dev, nullptr, nullptr, stream)
+                       : polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
+                                              info_dev, rank_dev, stream);
     return rc ? hip_fail("list decode launch", (hipError_t)rc) : 0;
+}
+}  // namespace
+
+int polar_sc_decode_list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                 uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
+{
+    return list_to_info(p, llr_dev, batch, list_size, 8, crc_poly, crc_len, info_dev, rank_dev, stream);
+}
+
+int polar_sc_decode_list_wide_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                      uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
+                                      void *stream)
+{
+    return list_to_info(p, llr_dev, batch, list_size, 32, crc_poly, crc_len, info_dev, rank_dev, stream);
 }
 
 // ---- adaptive CRC-aided decoding (include/polar_sc.h) -----------------------------
@@ -1474,12 +1498,14 @@ int polar_sc_adaptive_workspace(const polar_sc_plan *p, size_t batch, size_t *by
     return 0;
 }
 
-int polar_sc_decode_adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
-                                     uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev,
-                                     uint8_t *rank_dev, uint8_t *stage_dev, void *stream)
+namespace {
+// the one body of the adaptive entries: max_list = 8 (the narrow kernel only) or 32
+int adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size, int max_list,
+                     uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev, uint8_t *rank_dev,
+                     uint8_t *stage_dev, void *stream)
 {
     if (!p) return -EINVAL;
-    if (list_size != 1 && list_size != 2 && list_size != 4 && list_size != 8) return -EINVAL;
+    if (list_size < 1 || list_size > max_list || (list_size & (list_size - 1))) return -EINVAL;
     if (const int rc = crc_args(p, crc_poly, crc_len)) return rc;
     if (batch == 0) return 0;
     if (!llr_dev || !info_dev || ((uintptr_t)llr_dev & 3u) || ((uintptr_t)info_dev & 7u)) return -EINVAL;
@@ -1497,9 +1523,28 @@ int polar_sc_decode_adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_d
     int rc = polar_sc_launch_crc_check(h, info_dev, batch, p->K, (uint32_t)crc_len, stage_dev, 0u, rank_dev, idx, count,
                                        stream);
     if (rc) return hip_fail("CRC check launch", (hipError_t)rc);
-    rc = polar_sc_launch_list_indexed(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len, info_dev,
-                                      rank_dev, idx, count, stream);
+    rc = list_size > 8 ? polar_sc_launch_list_wide(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly,
+                                                   (uint32_t)crc_len, info_dev, rank_dev, idx, count, stream)
+                       : polar_sc_launch_list_indexed(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly,
+                                                      (uint32_t)crc_len, info_dev, rank_dev, idx, count, stream);
     return rc ? hip_fail("indexed list decode launch", (hipError_t)rc) : 0;
+}
+}  // namespace
+
+int polar_sc_decode_adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                     uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev,
+                                     uint8_t *rank_dev, uint8_t *stage_dev, void *stream)
+{
+    return adaptive_to_info(p, llr_dev, batch, list_size, 8, crc_poly, crc_len, workspace, info_dev, rank_dev, stage_dev,
+                            stream);
+}
+
+int polar_sc_decode_adaptive_wide_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                          uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev,
+                                          uint8_t *rank_dev, uint8_t *stage_dev, void *stream)
+{
+    return adaptive_to_info(p, llr_dev, batch, list_size, 32, crc_poly, crc_len, workspace, info_dev, rank_dev,
+                            stage_dev, stream);
 }
 
 int polar_sc_decode(const polar_sc_plan *p, const int8_t *llr_dev, uint64_t *hard_bits_dev,

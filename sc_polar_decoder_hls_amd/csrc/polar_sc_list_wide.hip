@@ -1,0 +1,532 @@
+// polar_sc_list_wide.hip -- successive-cancellation list decoding with 16 and 32 paths (gfx950).
+// The decoding rule is that of polar_sc_list.hip, bit for bit; the state layout is
+// this kernel's own, because a list of 32 does not fit the 3-bit fields, the key and the LDS budget
+// of the narrow kernel.
+//
+// One wave decodes one frame; waves never synchronise with each other. The wave's share of LDS:
+//   R        the channel LLRs as int16 (level LOGN of the tree, shared by every path)
+//   A[p][s]  LLR arrays: level s = 1 .. LOGN-2 (a node of 2^s LLRs) of physical array p, int16, at
+//            element 2^s: N bytes per array
+//   B[p][s]  partial sums of the completed left child at level s of physical array p, bit-packed
+//   T        per rank {PM, a_lo, a_hi, b_lo, b_hi, bit}, in two copies
+// Level LOGN-1 of the LLRs is never stored. It would be half of every array, and only the level
+// below reads it, at four leaves of a frame (0, N/4, N/2, 3N/4): those steps compute their input
+// pairs in registers from R. For leaves below N/2 the level is F(R[e], R[e + N/2]), the same for
+// every path; from N/2 on it is G(R[e], R[e + N/2], beta) with beta the path's level-(LOGN-1)
+// partial sums, found through index word b.
+//
+// Paths share arrays through two 64-bit index words per rank, 5 bits per level: word `a` names the
+// physical array that holds the path's LLRs of levels 1 .. LOGN-2, word `b` the one that holds its
+// partial sums of levels 0 .. LOGN-1 (50 bits at N = 1024). All live paths walk the tree in
+// lockstep, so a level is rewritten by every path at once, what it held is dead for every path, and
+// rank j takes physical array j for it. A fork copies index words and nothing else.
+//
+// An information leaf has 2 * paths <= 64 candidates: candidate 2 r + bit sits in lane 2 r + bit
+// with the key PM' << 6 | r << 1 | bit (PM' < 2^25, so the key stays below the 0xFFFFFFFF of an idle
+// lane). Keys are unique; the number of smaller keys, counted over 2 L lanes read one by one, is
+// the destination rank. The bit fold, the transform, the compression by the plan's table, the CRC
+// and the row store are those of the narrow kernel at wider counts.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace polar_list_wide {
+
+typedef uint32_t u32;
+typedef unsigned long long u64;
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+// the per-dword record of the plan's transform table (polar_sc_xform.hip polar_xf::Ent)
+struct __attribute__((aligned(32))) Ent {
+    u32 m, off, mv[5], pc;
+};
+
+constexpr int GMAX = 32767;     // |G| bound of the rule
+constexpr int FB = 5;           // bits of a field of an index word
+
+// dword of level s inside a path's partial-sum array: levels 0..4 take a dword each, level
+// s >= 5 takes 2^(s-5)
+__host__ __device__ constexpr int boff(int s) { return s < 5 ? s : 4 + (1 << (s - 5)); }
+
+// a 1 in each of the 12 fields of an index word
+__host__ __device__ constexpr u64 field_ones()
+{
+    u64 w = 0;
+    for (int k = 0; k < 12; k++) w |= 1ull << (FB * k);
+    return w;
+}
+
+template <int LOGN, int L>
+struct Shape {
+    static constexpr int N = 1 << LOGN;
+    static constexpr int D = N / 32;                  // dwords of a codeword
+    static constexpr int R_DW = N / 2;                // channel LLRs, int16
+    static constexpr int A_DW = N / 4;                // per physical array: levels 1 .. LOGN-2 (dword 0 unused)
+    static constexpr int B_DW = boff(LOGN) + D;       // levels 0 .. LOGN
+    static constexpr int T_DW = 2 * 6 * L;            // two copies of {pm, a_lo, a_hi, b_lo, b_hi, bit}[L]
+    static constexpr int WAVE_DW = R_DW + L * A_DW + L * B_DW + T_DW;
+    // waves per block: 4 where four fit the 64 KB of a block's static LDS, else as many as fit
+    static constexpr int FIT = 16384 / WAVE_DW;
+    static constexpr int WPB = FIT >= 4 ? 4 : FIT;
+    static constexpr int IROW = D < 2 ? 2 : D;        // information-row image per path (dwords), inside A
+    static_assert(LOGN >= 5 && LOGN <= 10 && (L == 16 || L == 32), "N = 32 .. 1024, 16 or 32 paths");
+    static_assert(WPB >= 1, "a wave's state fits a block's static LDS");
+    static_assert(IROW <= A_DW, "the information image reuses the LLR arrays");
+    static_assert(FB * LOGN <= 64, "a field per level in a 64-bit word");
+};
+
+// orders the phases of the wave's LDS state: LDS executes one wave's instructions in order, so only
+// the compiler has to be held
+__device__ __forceinline__ void wave_phase()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ s16x2 as_pk(u32 x) { return __builtin_bit_cast(s16x2, x); }
+__device__ __forceinline__ u32 as_u(s16x2 x) { return __builtin_bit_cast(u32, x); }
+// (no operand is ever -32768: the channel is int8 and G clamps at +-32767)
+__device__ __forceinline__ s16x2 pk_abs(s16x2 v) { return __builtin_elementwise_max(v, -v); }
+
+// F of two LLR pairs: sign(a) sign(b) min(|a|, |b|); min gives the 0 of a zero operand
+__device__ __forceinline__ u32 f_pk(u32 a, u32 b)
+{
+    const s16x2 va = as_pk(a), vb = as_pk(b);
+    const s16x2 m = __builtin_elementwise_min(pk_abs(va), pk_abs(vb));
+    const s16x2 sg = (va ^ vb) >> 15;
+    return as_u((m ^ sg) - sg);
+}
+
+// G of two LLR pairs, u = bits 0 and 1: clamp(b + (u ? -a : a)); the saturating packed add stops at
+// -32768, the max brings that to -32767
+__device__ __forceinline__ u32 g_pk(u32 a, u32 b, u32 u)
+{
+    const s16x2 um = as_pk(((0u - (u & 1u)) & 0xFFFFu) | ((0u - ((u >> 1) & 1u)) << 16));
+    const s16x2 sa = (as_pk(a) ^ um) - um;
+    const s16x2 lo = {-GMAX, -GMAX};
+    return as_u(__builtin_elementwise_max(__builtin_elementwise_add_sat(as_pk(b), sa), lo));
+}
+
+__device__ __forceinline__ int f_one(int a, int b)
+{
+    const int m = min(abs(a), abs(b));
+    return ((a ^ b) < 0) ? -m : m;
+}
+
+__device__ __forceinline__ int g_one(int a, int b, u32 u)
+{
+    return min(max(b + (u ? -a : a), -GMAX), GMAX);   // (one v_med3_i32)
+}
+
+__device__ __forceinline__ u32 field(u64 w, int s) { return (u32)(w >> (FB * s)) & 31u; }
+
+// bits under e.m packed at the low end (polar_sc_xform.hip compress)
+__device__ __forceinline__ u32 compress(u32 x, const Ent &e)
+{
+    x &= e.m;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const u32 t = x & e.mv[i];
+        x = (x ^ t) | (t >> (1 << i));
+    }
+    return x;
+}
+
+__device__ __forceinline__ Ent load_ent(const Ent *__restrict__ tab, u32 d)
+{
+    const uint4 *q = (const uint4 *)(tab + d);
+    const uint4 a = q[0], b = q[1];
+    Ent e;
+    e.m = a.x; e.off = a.y; e.mv[0] = a.z; e.mv[1] = a.w;
+    e.mv[2] = b.x; e.mv[3] = b.y; e.mv[4] = b.z; e.pc = b.w;
+    return e;
+}
+
+// how a node step gets level s + 1: from the arrays, or (s = LOGN - 2) from the channel by F or G
+enum Top { STORED = 0, TOP_F = 1, TOP_G = 2 };
+
+// The state of one frame; every member function is called by the whole wave.
+template <int LOGN, int L>
+struct Wave {
+    typedef Shape<LOGN, L> S;
+    u32 *R, *A, *B, *T;
+    u32 lane;
+    int count;      // live paths (wave-uniform)
+    int cur;        // which copy of T is current
+
+    __device__ __forceinline__ u32 *tab_pm(int c) { return T + c * 6 * L; }
+    __device__ __forceinline__ u32 *tab_bit(int c) { return T + c * 6 * L + 5 * L; }
+    __device__ __forceinline__ u64 word_a(int c, u32 r)
+    {
+        const u32 *t = T + c * 6 * L + L;
+        return (u64)t[r] | ((u64)t[L + r] << 32);
+    }
+    __device__ __forceinline__ u64 word_b(int c, u32 r)
+    {
+        const u32 *t = T + c * 6 * L + 3 * L;
+        return (u64)t[r] | ((u64)t[L + r] << 32);
+    }
+    __device__ __forceinline__ void set_words(int c, u32 r, u64 a, u64 b)
+    {
+        u32 *t = T + c * 6 * L + L;
+        t[r] = (u32)a;
+        t[L + r] = (u32)(a >> 32);
+        t[2 * L + r] = (u32)b;
+        t[3 * L + r] = (u32)(b >> 32);
+    }
+
+    // LLR pair x (0 <= x < N/4) of the virtual level LOGN - 1 of the path whose word b is ib
+    template <int TOP>
+    __device__ __forceinline__ u32 top_pair(int x, u64 ib)
+    {
+        const u32 ra = R[x], rb = R[x + S::N / 4];
+        if (TOP == TOP_F) return f_pk(ra, rb);
+        const u32 q = field(ib, LOGN - 1);
+        return g_pk(ra, rb, B[q * S::B_DW + boff(LOGN - 1) + (x >> 4)] >> ((2 * x) & 31));
+    }
+
+    // level s (1 <= s <= LOGN - 2) of every live path from level s + 1: count * 2^(s-1) LLR pairs
+    // over the 64 lanes. F reads the path's own array (written by the step before), G the array the
+    // index word names and the partial sums of its left child; TOP != STORED (s = LOGN - 2 only)
+    // takes level s + 1 from the channel instead.
+    template <bool IS_G, int TOP>
+    __device__ __forceinline__ void node(int s)
+    {
+        const int sh = s - 1, half = 1 << sh, total = count << sh;
+        for (int w = (int)lane; w < total; w += 64) {
+            const int j = w >> sh, e = w & (half - 1);
+            const u64 ib = (IS_G || TOP == TOP_G) ? word_b(cur, j) : 0ull;
+            u32 a, b, u = 0;
+            if (TOP == STORED) {
+                const u32 p = IS_G ? field(word_a(cur, j), s + 1) : (u32)j;
+                const u32 *in = A + p * S::A_DW + (1 << s);
+                a = in[e];
+                b = in[e + half];
+            } else {
+                a = top_pair<TOP>(e, ib);
+                b = top_pair<TOP>(e + half, ib);
+            }
+            if (IS_G) u = B[field(ib, s) * S::B_DW + boff(s) + (e >> 4)] >> ((2 * e) & 31);
+            A[j * S::A_DW + half + e] = IS_G ? g_pk(a, b, u) : f_pk(a, b);
+        }
+        wave_phase();
+    }
+
+    // the levels leaf i (even) needs below its lowest set bit, down to level 1
+    __device__ __forceinline__ void descend(u32 i)
+    {
+        constexpr int TS = LOGN - 2;      // the highest stored level
+        int t;
+        if (i == 0u) {
+            node<false, TOP_F>(TS);
+            t = TS;
+        } else {
+            t = __builtin_ctz(i);
+            if (t == LOGN - 1) {          // i = N/2: G of the virtual level, then F
+                node<false, TOP_G>(TS);
+                t = TS;
+            } else if (t == TS) {         // i = N/4 or 3N/4
+                if (i < (u32)S::N / 2u) node<true, TOP_F>(TS);
+                else node<true, TOP_G>(TS);
+            } else {
+                node<true, STORED>(t);
+            }
+        }
+        for (int s = t - 1; s >= 1; s--) node<false, STORED>(s);
+    }
+
+    // the LLR of leaf i for path r (r < count): F or G of the level-1 pair
+    __device__ __forceinline__ int leaf_llr(u32 i, u32 r)
+    {
+        if (!(i & 1u)) {
+            const u32 v = A[r * S::A_DW + 1];
+            return f_one((short)(v & 0xFFFFu), (short)(v >> 16));
+        }
+        const u32 v = A[field(word_a(cur, r), 1) * S::A_DW + 1];
+        const u32 u = B[field(word_b(cur, r), 0) * S::B_DW] & 1u;
+        return g_one((short)(v & 0xFFFFu), (short)(v >> 16), u);
+    }
+
+    __device__ __forceinline__ void frozen_leaf(u32 i)
+    {
+        if ((int)lane < count) {
+            const int lam = leaf_llr(i, lane);
+            tab_pm(cur)[lane] += lam < 0 ? (u32)(-lam) : 0u;
+            tab_bit(cur)[lane] = 0u;
+        }
+        wave_phase();
+    }
+
+    // candidates 2 r + bit in lanes 0 .. 2 count - 1; the survivors go to the other copy of T
+    __device__ __forceinline__ void info_leaf(u32 i)
+    {
+        const u32 r = lane >> 1, bit = lane & 1u;
+        const bool valid = (int)r < count;
+        u32 key = 0xFFFFFFFFu, pm = 0;
+        u64 ia = 0, ib = 0;
+        if (valid) {
+            const int lam = leaf_llr(i, r);
+            ia = word_a(cur, r);
+            ib = word_b(cur, r);
+            pm = tab_pm(cur)[r] + (bit != (u32)(lam < 0) ? (u32)abs(lam) : 0u);
+            key = (pm << 6) | (r << 1) | bit;
+        }
+        u32 dest = 0;
+#pragma unroll
+        for (int k = 0; k < 2 * L; k++) dest += (u32)__builtin_amdgcn_readlane((int)key, k) < key ? 1u : 0u;
+        const int nxt = cur ^ 1;
+        if (valid && dest < (u32)L) {
+            tab_pm(nxt)[dest] = pm;
+            set_words(nxt, dest, ia, ib);
+            tab_bit(nxt)[dest] = bit;
+        }
+        cur = nxt;
+        count = min(L, 2 * count);
+        wave_phase();
+    }
+
+    // fold the bit decided at leaf i into the partial sums: t = the level of the first ancestor that
+    // is a left child (LOGN after the last leaf). Levels below 5 fold in a register of lane j =
+    // rank j; higher ones in place in the destination, one dword per lane. Then rank j owns array j
+    // for that level of the partial sums and for the stored LLR levels among 1 .. t, which the next
+    // leaf rewrites.
+    __device__ __forceinline__ void fold_bits(u32 i)
+    {
+        const int t = (i + 1u == (u32)S::N) ? LOGN : __builtin_ctz(i + 1u);
+        const bool live = (int)lane < count;
+        u64 ib = 0;
+        if (live) {
+            ib = word_b(cur, lane);
+            u32 beta = tab_bit(cur)[lane];
+            const int ts = t < 5 ? t : 5;
+            for (int s = 0; s < ts; s++) {
+                const u32 bl = B[field(ib, s) * S::B_DW + s];
+                beta = (bl ^ beta) | (beta << (1 << s));
+            }
+            B[lane * S::B_DW + boff(t)] = beta;
+        }
+        wave_phase();
+        for (int s = 5; s < t; s++) {
+            const int sh = s - 5, w = 1 << sh, total = count << sh;
+            for (int x = (int)lane; x < total; x += 64) {
+                const int j = x >> sh, d = x & (w - 1);
+                u32 *dst = B + j * S::B_DW + boff(t);
+                const u32 c = dst[d];
+                dst[d] = c ^ B[field(word_b(cur, j), s) * S::B_DW + boff(s) + d];
+                dst[w + d] = c;
+            }
+            wave_phase();
+        }
+        if (live && t < LOGN) {
+            const int ta = t < LOGN - 2 ? t : LOGN - 2;
+            const u64 am = ((1ull << (FB * ta + FB)) - 1ull) & ~31ull;      // fields 1 .. ta
+            const u64 ia = word_a(cur, lane);
+            set_words(cur, lane, (ia & ~am) | (((u64)lane * field_ones()) & am),
+                      (ib & ~(31ull << (FB * t))) | ((u64)lane << (FB * t)));
+        }
+        wave_phase();
+    }
+};
+
+// dwords of a codeword through u = x F^{(x)n}: the five stages inside a dword
+__device__ __forceinline__ u32 xf_dword(u32 w)
+{
+    w ^= (w >> 1) & 0x55555555u;
+    w ^= (w >> 2) & 0x33333333u;
+    w ^= (w >> 4) & 0x0F0F0F0Fu;
+    w ^= (w >> 8) & 0x00FF00FFu;
+    w ^= (w >> 16) & 0x0000FFFFu;
+    return w;
+}
+
+// CRC of the rule over an information row in LDS: register zero, no reflection, no final XOR;
+// message = bits 0 .. K-c-1 MSB first, check = bits K-c .. K-1 MSB first. One lane per path.
+__device__ __forceinline__ bool crc_passes(const u32 *row, u32 K, u32 poly, u32 c)
+{
+    const u32 top = 1u << (c - 1u), keep = c == 32u ? 0xFFFFFFFFu : (1u << c) - 1u;
+    const u32 msg = K - c;
+    u32 reg = 0, w = 0;
+    for (u32 k = 0; k < msg; k++) {
+        if (!(k & 31u)) w = row[k >> 5];
+        const u32 fb = ((reg & top) ? 1u : 0u) ^ (w & 1u);
+        w >>= 1;
+        reg = ((reg << 1) & keep) ^ (fb ? poly : 0u);
+    }
+    u32 bad = 0;
+    for (u32 m = 0; m < c; m++) {
+        const u32 k = msg + m;
+        bad |= ((row[k >> 5] >> (k & 31u)) ^ (reg >> (c - 1u - m))) & 1u;
+    }
+    return bad == 0u;
+}
+
+// INDEXED = false: wave slot f decodes frame f of the batch (idx and idx_count unused).
+// INDEXED = true: the indexed launch of adaptive decoding: slot s returns when
+// s >= *idx_count, else decodes frame idx[s]; an entry outside the batch is skipped, so that nothing
+// a wrong list holds can be used as an address.
+template <int LOGN, int L, bool INDEXED>
+__global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_wide_kernel(
+    const Ent *__restrict__ tab, const int8_t *__restrict__ llr, u32 batch, u32 K, u32 poly, u32 clen,
+    u32 *__restrict__ info, uint8_t *__restrict__ rank_out, const u32 *__restrict__ idx,
+    const u32 *__restrict__ idx_count)
+{
+    typedef Shape<LOGN, L> S;
+    constexpr int N = S::N;
+    __shared__ u32 lds[S::WPB * S::WAVE_DW];
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    size_t frame = (size_t)blockIdx.x * S::WPB + wave;
+    if (frame >= batch) return;                      // (wave-uniform; no block-wide barrier anywhere)
+    if constexpr (INDEXED) {
+        if (frame >= *idx_count) return;
+        frame = (size_t)__builtin_amdgcn_readfirstlane(idx[frame]);
+        if (frame >= batch) return;
+    }
+
+    Wave<LOGN, L> W;
+    W.R = lds + wave * S::WAVE_DW;
+    W.A = W.R + S::R_DW;
+    W.B = W.A + L * S::A_DW;
+    W.T = W.B + L * S::B_DW;
+    W.lane = lane;
+    W.count = 1;
+    W.cur = 0;
+
+    // the channel: N int8 -> int16 pairs, four LLRs per lane and step
+    const u32 *src = (const u32 *)(llr + frame * (size_t)N);
+    for (int q = (int)lane; q < N / 4; q += 64) {
+        const u32 v = src[q];
+        const int l0 = (int8_t)(v & 0xFFu), l1 = (int8_t)((v >> 8) & 0xFFu);
+        const int l2 = (int8_t)((v >> 16) & 0xFFu), l3 = (int8_t)(v >> 24);
+        W.R[2 * q] = ((u32)l0 & 0xFFFFu) | ((u32)l1 << 16);
+        W.R[2 * q + 1] = ((u32)l2 & 0xFFFFu) | ((u32)l3 << 16);
+    }
+    // rank 0: metric 0, every level in array 0
+    for (int x = (int)lane; x < S::T_DW; x += 64) W.T[x] = 0u;
+    wave_phase();
+
+    u32 mword = 0;
+    for (u32 i = 0; i < (u32)N; i++) {
+        if (!(i & 31u)) mword = tab[i >> 5].m;       // (uniform: a scalar load)
+        if (!(i & 1u)) W.descend(i);
+        if ((mword >> (i & 31u)) & 1u) W.info_leaf(i);
+        else W.frozen_leaf(i);
+        W.fold_bits(i);
+    }
+
+    // every path's codeword estimate sits in level LOGN of its own partial-sum array
+    constexpr int D = S::D, IROW = S::IROW;
+    const int count = W.count;
+    u32 *img = W.A;                                  // (the LLR arrays are dead)
+    for (int x = (int)lane; x < L * IROW; x += 64) img[x] = 0u;
+    for (int x = (int)lane; x < count * D; x += 64) {
+        u32 *p = W.B + (x / D) * S::B_DW + boff(LOGN) + (x % D);
+        *p = xf_dword(*p);
+    }
+    wave_phase();
+    for (int h = 1; h < D; h <<= 1) {                // the stages between dwords
+        for (int x = (int)lane; x < count * D; x += 64) {
+            const int d = x % D;
+            u32 *p = W.B + (x / D) * S::B_DW + boff(LOGN) + d;
+            if (!(d & h)) *p ^= p[h];
+        }
+        wave_phase();
+    }
+    for (int x = (int)lane; x < count * D; x += 64) {
+        const int j = x / D, d = x % D;
+        const Ent e = load_ent(tab, (u32)d);
+        const u32 c = compress(W.B[j * S::B_DW + boff(LOGN) + d], e);
+        u32 *row = img + j * IROW;
+        const u32 sh = e.off & 31u, q = e.off >> 5;
+        if (e.pc) atomicOr(&row[q], c << sh);
+        if (sh + e.pc > 32u) atomicOr(&row[q + 1u], c >> (32u - sh));
+    }
+    wave_phase();
+
+    bool pass = false;
+    if (clen && (int)lane < count) pass = crc_passes(img + lane * IROW, K, poly, clen);
+    const unsigned long long votes = __ballot(pass);
+    const u32 pick = votes ? (u32)__builtin_ctzll(votes) : 0u;
+    const u32 irow = 2u * ((K + 63u) / 64u);
+    if (lane < irow) info[frame * irow + lane] = img[pick * IROW + lane];
+    if (rank_out && lane == 0u) rank_out[frame] = (uint8_t)((clen && !votes) ? 0xFFu : pick);
+}
+
+// idx == nullptr: the direct kernel over frames 0 .. batch - 1; else the indexed kernel
+template <int LOGN, int L>
+void launch(hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly, u32 clen, u32 *info,
+            uint8_t *rank_out, const u32 *idx, const u32 *count)
+{
+    constexpr int WPB = Shape<LOGN, L>::WPB;
+    const dim3 blocks((unsigned)(((size_t)batch + WPB - 1) / WPB)), threads(64 * WPB);
+    if (idx)
+        hipLaunchKernelGGL((polar_sc_list_wide_kernel<LOGN, L, true>), blocks, threads, 0, s, tab, llr, batch, K, poly,
+                           clen, info, rank_out, idx, count);
+    else
+        hipLaunchKernelGGL((polar_sc_list_wide_kernel<LOGN, L, false>), blocks, threads, 0, s, tab, llr, batch, K, poly,
+                           clen, info, rank_out, idx, count);
+}
+
+template <int LOGN>
+void launch_l(int L, hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly, u32 clen,
+              u32 *info, uint8_t *rank_out, const u32 *idx, const u32 *count)
+{
+    if (L == 16) launch<LOGN, 16>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count);
+    else launch<LOGN, 32>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count);
+}
+
+template <int LOGN>
+void shape_l(int L, uint32_t *dw, uint32_t *wpb)
+{
+    if (L == 16) *dw = Shape<LOGN, 16>::WAVE_DW, *wpb = Shape<LOGN, 16>::WPB;
+    else *dw = Shape<LOGN, 32>::WAVE_DW, *wpb = Shape<LOGN, 32>::WPB;
+}
+
+}  // namespace polar_list_wide
+
+// tab_dev: the plan's transform table (polar_sc_xform_table). 32 <= N <= 1024 a power of two,
+// L = 16 or 32, 1 <= K <= N, clen = 0 (no CRC) or 1 <= clen <= 32 and < K, 1 <= batch <= 2^31 - 8.
+// idx_dev == NULL: every frame of the batch. Else only the frames idx_dev[0 .. *count_dev) (both
+// written earlier on `stream`; idx_dev holds `batch` entries): the info_dev and rank_dev rows of the
+// other frames are left alone. Returns 0 or a hipError_t.
+extern "C" int polar_sc_launch_list_wide(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
+                                         uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
+                                         uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
+                                         void *stream)
+{
+    using namespace polar_list_wide;
+    const hipStream_t s = (hipStream_t)stream;
+    const Ent *tab = (const Ent *)tab_dev;
+    const u32 b = (u32)batch;
+    u32 *info = (u32 *)info_dev;
+    switch (N) {
+    case 32: launch_l<5>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev, idx_dev, count_dev); break;
+    case 64: launch_l<6>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev, idx_dev, count_dev); break;
+    case 128: launch_l<7>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev, idx_dev, count_dev); break;
+    case 256: launch_l<8>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev, idx_dev, count_dev); break;
+    case 512: launch_l<9>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev, idx_dev, count_dev); break;
+    default: launch_l<10>(L, s, tab, llr_dev, b, K, poly, clen, info, rank_dev, idx_dev, count_dev); break;
+    }
+    return (int)hipGetLastError();
+}
+
+// static LDS per wave and waves per block of the kernel for (N, L), N = 32 .. 1024 a power of two,
+// L = 16 or 32 (zeros otherwise): the accounting of DESIGN.md 3.11
+extern "C" void polar_sc_list_wide_shape(uint32_t N, int L, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block)
+{
+    using namespace polar_list_wide;
+    uint32_t dw = 0, wpb = 0;
+    if (L == 16 || L == 32) {
+        switch (N) {
+        case 32: shape_l<5>(L, &dw, &wpb); break;
+        case 64: shape_l<6>(L, &dw, &wpb); break;
+        case 128: shape_l<7>(L, &dw, &wpb); break;
+        case 256: shape_l<8>(L, &dw, &wpb); break;
+        case 512: shape_l<9>(L, &dw, &wpb); break;
+        case 1024: shape_l<10>(L, &dw, &wpb); break;
+        default: break;
+        }
+    }
+    *lds_bytes_per_wave = dw * 4u;
+    *waves_per_block = wpb;
+}

@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Speed of adaptive CRC-aided decoding, HIP-event timed. Per shape and Eb/N0:
-decode_to_info, crc_check of its result, decode_list and decode_adaptive of the same frames (an
-8-bit CRC, L = 8), and the fraction of frames the adaptive call sent to the list decoder (stage 1).
+decode_to_info, crc_check of its result, and per list size of --lists (8, 16, 32) decode_list and
+decode_adaptive of the same frames (an 8-bit CRC), with the fraction of frames the adaptive call sent
+to the list decoder (stage 1) and the frame errors left at that list size.
 The frames are codewords of crc_attach payloads (256 distinct ones, repeated) through BPSK and AWGN,
 quantized as the reference's testbench does (beta 4, +-31). One warm-up of every way, a comparison
 of decode_adaptive with its two stages run apart, then --rounds interleaved rounds of --steps calls
 each; one JSON line per shape, Eb/N0 and way with the per-round times, their median and spread
-(max - min), and for decode_adaptive the sum it is expected to sit near: decode_to_info + crc_check
+(max - min), and for decode_adaptive the frame errors and the sum it is expected to sit near: decode_to_info + crc_check
 + stage-1 fraction x decode_list of the same run. Written to --out as well when given
 (profiles/adaptive_speed.jsonl).
 
-usage: python tools/adaptive_speed.py [--steps 10] [--rounds 5] [--shapes name:frames,...] [--ebn0 1,2,3] [--out FILE]
+usage: python tools/adaptive_speed.py [--steps 10] [--rounds 5] [--shapes name:frames,...] [--ebn0 1,2,3] [--lists 8,16,32]
+       [--out FILE]
 """
 import argparse
 import json
@@ -24,7 +26,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 SHAPES = "FB_N1024_K512:16384,FB_N128_K64:16384"
 CRC = (0x07, 8)
-L = 8
 
 
 def main():
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default=SHAPES)
     ap.add_argument("--ebn0", default="1,2,3")
+    ap.add_argument("--lists", default="8,16,32")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -61,20 +63,26 @@ def main():
         for db in (float(x) for x in args.ebn0.split(",")):
             sigma = 1.0 / (2.0 * dec.K / dec.N * 10.0 ** (db / 10.0)) ** 0.5
             v = pkg.quantize(bpsk + sigma * noise, 4, -31, 31)
+            lists = [int(x) for x in args.lists.split(",")]
             runs = {"decode_to_info": lambda: dec.decode_to_info(v, out=sc),
-                    "crc_check": lambda: dec.crc_check(sc, CRC, out=ok),
-                    "decode_list": lambda: dec.decode_list(v, L, crc=CRC, out=info, rank=rank),
-                    "decode_adaptive": lambda: dec.decode_adaptive(v, L, CRC, out=info, rank=rank, stage=stage,
-                                                                   workspace=ws)}
+                    "crc_check": lambda: dec.crc_check(sc, CRC, out=ok)}
+            for L in lists:
+                runs["decode_list L=%d" % L] = lambda L=L: dec.decode_list(v, L, crc=CRC, out=info, rank=rank)
+                runs["decode_adaptive L=%d" % L] = lambda L=L: dec.decode_adaptive(v, L, CRC, out=info, rank=rank,
+                                                                                   stage=stage, workspace=ws)
             for fn in runs.values():
                 for _ in range(2):
                     fn()
-            # (the last warm-up call was decode_adaptive: compare it with its stages run apart)
-            listed = dec.decode_list(v, L, crc=CRC)[0]
-            if not torch.equal(stage, 1 - ok) or not torch.equal(info, torch.where(ok[:, None] == 1, sc, listed)):
-                raise SystemExit("adaptive_speed: decode_adaptive differs from its stages at %s %.1f dB" % (name, db))
-            frac = float(stage.float().mean())
-            frame_errors = int((info != xw.new_tensor(words.view(np.int64))).any(dim=1).sum())
+            # compare decode_adaptive with its stages run apart, and count what it leaves wrong
+            frac, frame_errors = {}, {}
+            for L in lists:
+                runs["decode_adaptive L=%d" % L]()
+                listed = dec.decode_list(v, L, crc=CRC)[0]
+                if not torch.equal(stage, 1 - ok) or not torch.equal(info, torch.where(ok[:, None] == 1, sc, listed)):
+                    raise SystemExit("adaptive_speed: decode_adaptive differs from its stages at %s %.1f dB L=%d"
+                                     % (name, db, L))
+                frac[L] = float(stage.float().mean())
+                frame_errors[L] = int((info != xw.new_tensor(words.view(np.int64))).any(dim=1).sum())
             torch.cuda.synchronize()
             us = {k: [] for k in runs}
             for _ in range(args.rounds):
@@ -82,12 +90,15 @@ def main():
                     us[k].append(timed(torch, fn, args.steps))
             med = {k: statistics.median(t) for k, t in us.items()}
             for k, t in us.items():
-                rec = {"way": k, "mask": name, "N": dec.N, "K": dec.K, "frames": frames, "ebn0_db": db, "L": L,
+                L = int(k.split("=")[1]) if "=" in k else None
+                rec = {"way": k.split(" ")[0], "mask": name, "N": dec.N, "K": dec.K, "frames": frames, "ebn0_db": db, "L": L,
                        "crc": list(CRC), "steps": args.steps, "us_rounds": [round(x, 2) for x in t],
-                       "us": round(med[k], 2), "spread_us": round(max(t) - min(t), 2), "stage1_fraction": round(frac, 5)}
-                if k == "decode_adaptive":
-                    rec.update(expected_us=round(med["decode_to_info"] + med["crc_check"] + frac * med["decode_list"], 2),
-                               frame_errors=frame_errors, workspace_bytes=ws.numel())
+                       "us": round(med[k], 2), "spread_us": round(max(t) - min(t), 2),
+                       "stage1_fraction": round(frac[lists[0]], 5)}
+                if k.startswith("decode_adaptive"):
+                    rec.update(expected_us=round(med["decode_to_info"] + med["crc_check"]
+                                                 + frac[L] * med["decode_list L=%d" % L], 2),
+                               frame_errors=frame_errors[L], workspace_bytes=ws.numel())
                 lines.append(json.dumps(rec))
                 print(lines[-1], flush=True)
         dec.close()

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Speed of list decoding, HIP-event timed. Per shape: decode_list at L = 1, 2, 4
-and 8 (with an 8-bit CRC, so that the CRC pass over the candidates is in the time), next to
+"""Speed of list decoding, HIP-event timed. Per shape: decode_list at --lists (L = 1
+.. 8: the narrow kernel, 16 and 32: the wide-list kernel; with an 8-bit CRC, so that the CRC pass over the candidates is in the time), next to
 decode_to_info of the same frames for scale (plain SC in the reference datapath; a different
 decoding rule, so the outputs are not compared). One warm-up of every way, then --rounds
 interleaved rounds of --steps calls each; one JSON line per shape and way with the per-round
 times, their median and spread (max - min), frames per second, and for the list kernel its LDS
 per wave and waves per block. Written to --out as well when given
-(profiles/<round>_list_speed.jsonl).
+(profiles/list_wide_speed.jsonl).
 
-usage: python tools/list_speed.py [--steps 10] [--rounds 5] [--shapes name:frames,...] [--out FILE]
+usage: python tools/list_speed.py [--steps 10] [--rounds 5] [--shapes name:frames,...] [--lists 1,2,...] [--out FILE]
 """
 import argparse
 import json
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--shapes", default=SHAPES)
+    ap.add_argument("--lists", default="1,2,4,8,16,32")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -49,7 +50,7 @@ def main():
         info = torch.empty((frames, dec.info_words), dtype=torch.int64, device="cuda")
         rank = torch.empty((frames,), dtype=torch.uint8, device="cuda")
         runs = {"decode_to_info": lambda: dec.decode_to_info(v, out=info)}
-        for L in (1, 2, 4, 8):
+        for L in (int(x) for x in args.lists.split(",")):
             runs["decode_list L=%d" % L] = lambda L=L: dec.decode_list(v, L, crc=CRC, out=info, rank=rank)
         for fn in runs.values():
             for _ in range(2):
