@@ -452,11 +452,28 @@ __device__ __forceinline__ u32 sm8_pair(u32 lo, u32 hi)
 //        sign of the last of them that is not 0, and the sign bit of position 0 if all are.
 //        Carried as a mask m: m' = (sum + m < 0).
 // (-DPOLAR_LEAF_RECURSE: the recursion for these blocks too, for A/Bs)
+//
+// A run of K levels whose left child is all frozen, above a child of width WC = W >> K, is the same
+// add without being a REP block: no F, no decisions on the left, and the child's input at its
+// position j is the exact sum of the W / WC positions = j mod WC, whose zero keeps the sign of the
+// last partial sum that is not 0 (position B + j first, as the a operand of every level). The
+// butterfly leaves the total on every lane and the carried sign on the lanes of the block's first
+// WC positions, which see the partial sums in that order. The child is decided there, on
+// (|total|, m) -- its code reads positions relative to an aligned block only -- and its bits are
+// copied to the other W / WC - 1 sub-blocks (x_a ^ x_b = x_b on the left of every level): one
+// DPP move per level. WC = 1 is a REP block. (-DPOLAR_LEAF_ADD_RECURSE: the recursion)
 // ---------------------------------------------------------------------------------------
 #ifndef POLAR_LEAF_RECURSE
 constexpr bool LEAF_BLOCKS = EXT;
 #else
 constexpr bool LEAF_BLOCKS = false;
+#endif
+// (-DPOLAR_REP_FALLBACK of the per-mask kernels stands for the kernel of before the REP carry as a
+// whole, polar_sc_jit.cpp kMaskFormsSrc: it takes the former leaf with it)
+#if !defined(POLAR_LEAF_ADD_RECURSE) && !defined(POLAR_REP_FALLBACK)
+constexpr bool LEAF_ADD = LEAF_BLOCKS;
+#else
+constexpr bool LEAF_ADD = false;
 #endif
 // what the packed 16-bit halves of the two block decoders rely on; a block whose bound misses
 // it takes the recursion
@@ -472,7 +489,22 @@ struct LeafBlock {
     // into the other half, and sum + m keeps its sign in 16 bits
     static constexpr u32 BIAS = (1u << (QB + 2)) * (u32)P16;
     static constexpr bool REP_OK = BIAS > MMAX + 1u && (u32)W * (BIAS + MMAX) < 0x10000u && (u32)W * MMAX + 1u < 0x8000u;
+    // a run of frozen-left levels adds n = W / WC values per child position: the same three
+    // conditions with n summands (REP_OK is add_ok(W))
+    static constexpr bool add_ok(u32 n) { return BIAS > MMAX + 1u && n * (BIAS + MMAX) < 0x10000u && n * MMAX + 1u < 0x8000u; }
 };
+// levels of the run of all-frozen left children that starts at block (B, W) of pattern fb
+// (the block holds information positions)
+constexpr int leaf_add_levels(u32 fb, int B, int W)
+{
+    int k = 0;
+    while (W >= 2 && ((fb >> B) & ((1u << (W / 2)) - 1u)) == 0u) {
+        B += W / 2;
+        W /= 2;
+        ++k;
+    }
+    return k;
+}
 static_assert(P16 > 1 || (LeafBlock<4>::SPC_OK && LeafBlock<8>::SPC_OK && LeafBlock<4>::REP_OK && LeafBlock<8>::REP_OK),
               "PAR <= 16: both block decoders at every LLR_BITS 5..9");
 // the lane that holds word position p (lane_pos is an involution)
@@ -489,6 +521,36 @@ __device__ __forceinline__ void rep_level(u32 &v, u32 &m)
 {
     v += xorlane<H>(v);
     m = pk_sra(pk_sub(pk_add(v, m), (LeafBlock<W>::BIAS << K) * 0x00010001u), 15);
+}
+// levels K .. N of a run that starts at width W: distances H, H / 2, ..
+template <int W, int H, int K, int N>
+__device__ __forceinline__ void add_levels(u32 &v, u32 &m)
+{
+    rep_level<W, H, K>(v, m);
+    if constexpr (K < N) add_levels<W, H / 2, K + 1, N>(v, m);
+}
+// the lanes of positions B + H .. B + 2 H - 1 take x from the position H below; the lanes of
+// positions B .. B + H - 1 keep theirs (a bank of the DPP bank mask is a quad of lanes; the
+// quads of positions 4..7 and 12..15 are mirrored under POLAR_LANE_REMAP)
+template <int B, int H>
+__device__ __forceinline__ u32 copy_up(u32 x)
+{
+    if constexpr (H == 8) {
+        return __builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xC, false);                 // row_ror:8
+    } else if constexpr (H == 4) {
+        static_assert((B & 7) == 0, "aligned block of 8");
+        return __builtin_amdgcn_update_dpp(x, x, POLAR_LANE_REMAP ? 0x141 : 0x114, 0xF, 1 << (B / 4 + 1), false);   // row_half_mirror / row_shr:4
+    } else {
+        static_assert(H == 2 && (B & 3) == 0, "aligned block of 4");
+        return __builtin_amdgcn_update_dpp(0u, x, (POLAR_LANE_REMAP && (B & 4)) ? 0xEE : 0x44, 0xF, 0xF, true);      // quad_perm [2,3,2,3] / [0,1,0,1]
+    }
+}
+// x of the first WC positions of block (B, W) to all of it
+template <int B, int WC, int W>
+__device__ __forceinline__ u32 copy_block(u32 x)
+{
+    if constexpr (WC < W) return copy_block<B, 2 * WC, W>(copy_up<B, WC>(x));
+    else return x;
 }
 
 template <u32 FB, int B, int W>
@@ -524,6 +586,19 @@ __device__ __forceinline__ u32 leaf_ms(u32 M, u32 S, const Lanes &ln)
             rep_level<W, 1, 2>(v, m);
         }
         return row_bcast<lane_of_pos(B)>(m);
+    } else if constexpr (LEAF_ADD && W >= 4 && leaf_add_levels(FB, B, W) >= 1 &&
+                         LeafBlock<W>::add_ok((u32)1 << leaf_add_levels(FB, B, W))) {
+        constexpr int K = leaf_add_levels(FB, B, W), WC = W >> K;
+        u32 v = pk_mad_u16(M, S | 0x00010001u, LeafBlock<W>::BIAS * 0x00010001u);
+        u32 m = S;
+        add_levels<W, W / 2, 1, K>(v, m);
+        if constexpr (WC == 1) {
+            return row_bcast<lane_of_pos(B)>(m);
+        } else {
+            // the child, moved to the block's first WC positions (where m is carried)
+            const u32 Mc = pk_abs_i16(pk_sub(v, (LeafBlock<W>::BIAS << K) * 0x00010001u));
+            return copy_block<B, WC, W>(leaf_ms<(FB >> (W - WC)), B, WC>(Mc, m, ln));
+        }
     } else if constexpr (W == 2) {
         if constexpr ((sub >> B) == 1u) {
             return (S ^ xorlane<1>(S)) & ln.a1;                 // (1, 0): x = [sa ^ sb, 0]
