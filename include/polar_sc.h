@@ -414,14 +414,14 @@ int polar_sc_decode_list_to_info(const polar_sc_plan *plan, const int8_t *llr_de
 
 /* The same call for list_size in {1, 2, 4, 8, 16, 32}: arguments, results, rule and error codes are
  * those of polar_sc_decode_list_to_info (rank_dev holds 0 .. list_size - 1, or 0xFF). list_size <= 8
- * is that call unchanged; 16 and 32 launch the wide-list kernel (one wave per frame, 5-bit index
- * fields, the top LLR level computed from the channel instead of stored: DESIGN.md 3.11). */
+ * is that call unchanged; 16 and 32 run the wide layout of the same kernel (one wave per frame,
+ * 5-bit index fields, the top LLR level computed from the channel instead of stored: DESIGN.md 3.11). */
 int polar_sc_decode_list_wide_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int list_size,
                                       uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
                                       void *stream);
 
-/* Static LDS per wave (bytes) and waves per block of the wide-list kernel for N = 32 .. 1024 (a
- * power of two) and list_size 16 or 32; zeros for anything else. Host only. */
+/* Static LDS per wave (bytes) and waves per block of the list kernel's wide layout for N = 32 .. 1024
+ * (a power of two) and list_size 16 or 32; zeros for anything else. Host only. */
 void polar_sc_list_wide_shape(uint32_t N, int list_size, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block);
 
 /* ---- Adaptive CRC-aided decoding, N <= 1024 ----

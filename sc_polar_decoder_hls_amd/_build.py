@@ -15,15 +15,14 @@ SOURCES = [os.path.join(PKG, "csrc", "polar_sc_kernels.hip"), os.path.join(PKG, 
            os.path.join(PKG, "csrc", "polar_sc_jit.cpp"), os.path.join(PKG, "csrc", "polar_sc_pairgen.cpp"),
            os.path.join(PKG, "csrc", "polar_sc_channel.hip"), os.path.join(PKG, "csrc", "polar_sc_xform.hip"),
            os.path.join(PKG, "csrc", "polar_sc_soft.hip"), os.path.join(PKG, "csrc", "polar_sc_tables.cpp"),
-           os.path.join(PKG, "csrc", "polar_sc_list.hip"), os.path.join(PKG, "csrc", "polar_sc_adaptive.hip"),
-           os.path.join(PKG, "csrc", "polar_sc_list_wide.hip")]
+           os.path.join(PKG, "csrc", "polar_sc_list.hip"), os.path.join(PKG, "csrc", "polar_sc_adaptive.hip")]
 SOFT_SRC = os.path.join(PKG, "csrc", "polar_sc_soft.hip")
 DEVICE_H = os.path.join(PKG, "csrc", "polar_sc_device.h")
 INTERP_H = os.path.join(PKG, "csrc", "polar_sc_interp.h")
 PAIR_H = os.path.join(PKG, "csrc", "polar_sc_pair.h")
 QUANT_H = os.path.join(PKG, "csrc", "polar_sc_quant.h")
 HEADERS = [os.path.join(ROOT, "include", "polar_sc.h"), DEVICE_H, INTERP_H, PAIR_H, os.path.join(PKG, "csrc", "polar_sc_plan.hpp"),
-           os.path.join(PKG, "csrc", "polar_sc_glibcf.h"), QUANT_H]
+           os.path.join(PKG, "csrc", "polar_sc_glibcf.h"), QUANT_H, os.path.join(PKG, "csrc", "polar_sc_xf.h")]
 GEN_DIR = os.path.join(PKG, "build")
 CLI_SRC = os.path.join(ROOT, "examples", "polar_decode_cli.c")
 CLI = os.path.join(PKG, "lib", "polar_decode_cli")

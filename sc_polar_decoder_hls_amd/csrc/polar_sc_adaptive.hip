@@ -22,22 +22,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "polar_sc_xf.h"
+
 namespace polar_adaptive {
 
-typedef uint32_t u32;
+using polar_xf::u32;
+using polar_xf::wave_phase;
 
 constexpr int CH = 8;               // dwords of a row per chunk
 constexpr int STRIDE = CH + 1;      // of a staged row in LDS (odd: lane-per-row reads spread over all banks)
 constexpr int WPB = 4;              // waves per block
 constexpr int WAVE_DW = 64 * STRIDE;
-
-// (as polar_sc_list.hip: LDS executes one wave's instructions in order, only the compiler has to be held)
-__device__ __forceinline__ void wave_phase()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // H: [hw][CP] dwords, hw a multiple of CH. info: [batch][rs] dwords. flag (may be null): per row
 // `pass_value` when it passes, 1 - pass_value when it fails. zero (may be null): per row a 0 byte

@@ -32,24 +32,16 @@ extern "C" void polar_sc_xform_table(const uint8_t *mask, uint32_t N, uint32_t *
 extern "C" int polar_sc_launch_xform(int encode, const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev,
                                      uint32_t N, uint32_t K, size_t batch, void *stream);
 extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stream);
-// polar_sc_list.hip: the list decoder of N <= 1024 (reads the same mask table)
-extern "C" int polar_sc_launch_list_indexed(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
-                                            uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
-                                            uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
-                                            void *stream);
+// polar_sc_list.hip: the list decoder of N <= 1024, L = 1 .. 32 (reads the same mask table; idx_dev
+// NULL: every frame of the batch)
+extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
+                                    int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
+                                    const uint32_t *idx_dev, const uint32_t *count_dev, void *stream);
 extern "C" size_t polar_sc_crc_table_dwords(uint32_t K, uint32_t c);
 extern "C" void polar_sc_crc_table(uint32_t K, uint32_t poly, uint32_t c, uint32_t *tab);
 extern "C" int polar_sc_launch_crc_check(const void *tab_dev, const uint64_t *info_dev, size_t batch, uint32_t K,
                                          uint32_t c, uint8_t *flag_dev, uint32_t pass_value, uint8_t *zero_dev,
                                          uint32_t *idx_dev, uint32_t *count_dev, void *stream);
-extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
-                                    int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
-                                    void *stream);
-// polar_sc_list_wide.hip: the same rule with 16 or 32 paths (idx_dev NULL: every frame of the batch)
-extern "C" int polar_sc_launch_list_wide(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
-                                         uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
-                                         uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
-                                         void *stream);
 // polar_sc_soft.hip: the stand-alone quantizer (0 or a hipError_t; arguments checked here)
 extern "C" int polar_sc_launch_quantize(const void *v_dev, int dtype, size_t n, int beta, int vsatn, int vsatp,
                                         void *q_dev, int bits, void *stream);
@@ -1421,7 +1413,7 @@ int polar_sc_decode_soft_to_info(const polar_sc_plan *p, const void *v_dev, int 
 }
 
 namespace {
-// the one body of the list entries: max_list = 8 (the narrow kernel only) or 32
+// the one body of the list entries: max_list = 8 (the narrow layout only) or 32
 int list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size, int max_list,
                  uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
 {
@@ -1436,11 +1428,8 @@ int list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, in
     if (batch > (size_t)0x7FFFFFF8) return -EINVAL;
     const void *tab = nullptr;
     if (const int e = ensure_xform(p, &tab)) return e;
-    const int rc = list_size > 8
-                       ? polar_sc_launch_list_wide(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly,
-                                                   (uint32_t)crc_len, info_dev, rank_dev, nullptr, nullptr, stream)
-                       : polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
-                                              info_dev, rank_dev, stream);
+    const int rc = polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
+                                        info_dev, rank_dev, nullptr, nullptr, stream);
     return rc ? hip_fail("list decode launch", (hipError_t)rc) : 0;
 }
 }  // namespace
@@ -1499,7 +1488,7 @@ int polar_sc_adaptive_workspace(const polar_sc_plan *p, size_t batch, size_t *by
 }
 
 namespace {
-// the one body of the adaptive entries: max_list = 8 (the narrow kernel only) or 32
+// the one body of the adaptive entries: max_list = 8 (the narrow layout only) or 32
 int adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size, int max_list,
                      uint32_t crc_poly, int crc_len, void *workspace, uint64_t *info_dev, uint8_t *rank_dev,
                      uint8_t *stage_dev, void *stream)
@@ -1523,10 +1512,8 @@ int adaptive_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch
     int rc = polar_sc_launch_crc_check(h, info_dev, batch, p->K, (uint32_t)crc_len, stage_dev, 0u, rank_dev, idx, count,
                                        stream);
     if (rc) return hip_fail("CRC check launch", (hipError_t)rc);
-    rc = list_size > 8 ? polar_sc_launch_list_wide(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly,
-                                                   (uint32_t)crc_len, info_dev, rank_dev, idx, count, stream)
-                       : polar_sc_launch_list_indexed(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly,
-                                                      (uint32_t)crc_len, info_dev, rank_dev, idx, count, stream);
+    rc = polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len, info_dev,
+                              rank_dev, idx, count, stream);
     return rc ? hip_fail("indexed list decode launch", (hipError_t)rc) : 0;
 }
 }  // namespace

@@ -1,15 +1,15 @@
 // polar_sc_list.hip -- successive-cancellation list decoding (gfx950): the L best paths of the SC
-// tree, ranked by an integer path metric, with an optional CRC inside the payload choosing the
-// survivor; int8 LLRs in, information words out, one launch. DESIGN.md 3.11 defines the decoding
-// rule; this file follows it bit for bit.
+// tree (L = 1 .. 32), ranked by an integer path metric, with an optional CRC inside the payload
+// choosing the survivor; int8 LLRs in, information words out, one launch. DESIGN.md 3.11 defines the
+// decoding rule; this file follows it bit for bit.
 //
 // One wave decodes one frame; waves never synchronise with each other. All state of a frame lives
 // in the wave's share of LDS:
 //   R        the channel LLRs as int16 (level LOGN of the tree, shared by every path)
 //   A[p][s]  LLR arrays: level s (a node of 2^s LLRs) of physical array p, int16, at element 2^s
 //   B[p][s]  partial sums of the completed left child at level s of physical array p, bit-packed
-//   T        per rank: path metric, the two index words below, the bit decided last
-// Paths share arrays through two index words per rank (3 bits per level): word `a` names the
+//   T        per rank: path metric, the two index words below, the bit decided last; in two copies
+// Paths share arrays through two index words per rank, a field per level: word `a` names the
 // physical array that holds the path's LLRs of each level, word `b` the same for the partial sums.
 // Every live path walks the tree in lockstep, so a level is rewritten by all paths at once: what
 // the level held before is dead for every path, and rank j simply takes physical array j for it.
@@ -19,56 +19,46 @@
 // The walk is bit by bit (no node shortcuts). Leaf i first recomputes the levels below the lowest
 // set bit t of i: G of level t from the parent's arrays (wherever the index word says they are),
 // then F down to level 1, packed two int16 per lane; the leaf LLR itself is F or G of the level-1
-// pair, taken in a register. An information leaf ranks its 2 * paths candidates by the key
-// PM' << 4 | rank << 1 | bit (unique, so counting the smaller keys is the destination rank) and
-// scatters the survivors' state to their new ranks. Then the decided bits are folded into the
+// pair, taken in a register. An information leaf ranks its 2 * paths <= 64 candidates, candidate
+// 2 r + bit in lane 2 r + bit, by the key PM' << (field bits + 1) | r << 1 | bit. Keys are unique;
+// the number of smaller keys, counted over 2 L lanes read one by one, is the destination rank, and
+// the survivors' state is scattered to their new ranks. Then the decided bits are folded into the
 // partial sums: beta = (left ^ right, right) level by level up to the first level that is a left
 // child, where it is stored. After the last leaf that is the level-LOGN array: the codeword
 // estimate of every path, from which the information words come as in polar_sc_xform.hip
 // (transform, compress by the mask with the plan's per-dword table, OR into an LDS image).
+//
+// Two layouts of that state, chosen from L at compile time (Narrow and Wide below). L <= 8: 32-bit
+// index words of 3-bit fields, every LLR level 1 .. LOGN-1 stored. L = 16 and 32 do not fit those
+// fields, that key or that LDS budget: 64-bit index words of 5-bit fields (50 bits at N = 1024), and
+// level LOGN-1 of the LLRs is never stored. It would be half of every array, and only the level
+// below reads it, at four leaves of a frame (0, N/4, N/2, 3N/4): those steps compute their input
+// pairs in registers from R. For leaves below N/2 the level is F(R[e], R[e + N/2]), the same for
+// every path; from N/2 on it is G(R[e], R[e + N/2], beta) with beta the path's level-(LOGN-1)
+// partial sums, found through index word b.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "polar_sc_xf.h"
+
 namespace polar_list {
 
-typedef uint32_t u32;
+using polar_xf::compress;
+using polar_xf::Ent;
+using polar_xf::load_ent;
+using polar_xf::u32;
+using polar_xf::wave_phase;
+using polar_xf::xf_dword;
+typedef unsigned long long u64;
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-// the per-dword record of the plan's transform table (polar_sc_xform.hip polar_xf::Ent)
-struct __attribute__((aligned(32))) Ent {
-    u32 m, off, mv[5], pc;
-};
 
 constexpr int GMAX = 32767;     // |G| bound of the rule
 
 // dword of level s inside a path's partial-sum array: levels 0..4 take a dword each, level
 // s >= 5 takes 2^(s-5)
 __host__ __device__ constexpr int boff(int s) { return s < 5 ? s : 4 + (1 << (s - 5)); }
-
-template <int LOGN, int L>
-struct Shape {
-    static constexpr int N = 1 << LOGN;
-    static constexpr int D = N / 32;                  // dwords of a codeword
-    static constexpr int R_DW = N / 2;                // channel LLRs, int16
-    static constexpr int A_DW = N / 2;                // per physical array: levels 1 .. LOGN-1 (+ pad)
-    static constexpr int B_DW = boff(LOGN) + D;       // levels 0 .. LOGN
-    static constexpr int T_DW = 2 * 4 * L;            // two copies of {pm, a, b, bit}[L]
-    static constexpr int WAVE_DW = R_DW + L * A_DW + L * B_DW + T_DW;
-    // waves per block: 4 where they fit the 64 KB of a block's static LDS, else 1 (a CU holds
-    // 160 KB: single-wave blocks leave the least of it unused)
-    static constexpr int WPB = WAVE_DW * 4 * 4 <= 65536 ? 4 : 1;
-    static constexpr int IROW = D < 2 ? 2 : D;        // information-row image per path (dwords), inside A
-    static_assert(IROW <= A_DW, "the information image reuses the LLR arrays");
-};
-
-// orders the phases of the wave's LDS state: LDS executes one wave's instructions in order, so only
-// the compiler has to be held
-__device__ __forceinline__ void wave_phase()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ s16x2 as_pk(u32 x) { return __builtin_bit_cast(s16x2, x); }
 __device__ __forceinline__ u32 as_u(s16x2 x) { return __builtin_bit_cast(u32, x); }
@@ -105,70 +95,205 @@ __device__ __forceinline__ int g_one(int a, int b, u32 u)
     return min(max(b + (u ? -a : a), -GMAX), GMAX);   // (one v_med3_i32)
 }
 
-__device__ __forceinline__ u32 field(u32 w, int s) { return (w >> (3 * s)) & 7u; }
+// ---- the two layouts: what the list size forces, and the node steps that differ in substance.
+// W is the Wave below; every function is called by the whole wave. -----------------------------------
 
-// bits under e.m packed at the low end (polar_sc_xform.hip compress)
-__device__ __forceinline__ u32 compress(u32 x, const Ent &e)
-{
-    x &= e.m;
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const u32 t = x & e.mv[i];
-        x = (x ^ t) | (t >> (1 << i));
+// L <= 8: one dword per index word, T = two copies of {pm, a, b, bit}[L]
+template <int LOGN, int L>
+struct Narrow {
+    typedef u32 Word;
+    static constexpr int FB = 3;                      // bits of a field of an index word
+    static constexpr int WORD_DW = 1;
+    static constexpr int A_DW = (1 << LOGN) / 2;      // per physical array: levels 1 .. LOGN-1 (+ pad)
+    static constexpr int TOP_LEVEL = LOGN - 1;        // the highest stored LLR level
+    // waves per block: 4 where they fit the 64 KB of a block's static LDS, else 1 (a CU holds
+    // 160 KB: single-wave blocks leave the least of it unused)
+    static constexpr int wpb(int wave_dw) { return wave_dw * 4 * 4 <= 65536 ? 4 : 1; }
+    static_assert(L <= 8, "a 3-bit field names one of L arrays");
+
+    __device__ __forceinline__ static Word load(const u32 *t, u32 r) { return t[r]; }
+    __device__ __forceinline__ static void store(u32 *t, u32 r, Word w) { t[r] = w; }
+
+    // level s (1 <= s < LOGN) of every live path from level s + 1: count * 2^(s-1) LLR pairs over
+    // the 64 lanes. F reads the path's own array (written by the step before) or, at the top, the
+    // channel; G reads the array the index word names and the partial sums of its left child.
+    template <bool IS_G, class W>
+    __device__ __forceinline__ static void node(W &w, int s)
+    {
+        typedef typename W::S S;
+        const int sh = s - 1, half = 1 << sh, total = w.count << sh;
+        for (int x = (int)w.lane; x < total; x += 64) {
+            const int j = x >> sh, e = x & (half - 1);
+            const u32 *in;
+            u32 u = 0;
+            if (s + 1 == LOGN) {
+                in = w.R;
+            } else {
+                const u32 p = IS_G ? W::field(w.word_a(w.cur, j), s + 1) : (u32)j;
+                in = w.A + p * S::A_DW + (1 << s);
+            }
+            if (IS_G) {
+                const u32 q = W::field(w.word_b(w.cur, j), s);
+                u = w.B[q * S::B_DW + boff(s) + (e >> 4)] >> ((2 * e) & 31);
+            }
+            const u32 a = in[e], b = in[e + half];
+            w.A[j * S::A_DW + half + e] = IS_G ? g_pk(a, b, u) : f_pk(a, b);
+        }
+        wave_phase();
     }
-    return x;
-}
 
-__device__ __forceinline__ Ent load_ent(const Ent *__restrict__ tab, u32 d)
+    // the levels leaf i (even) needs below its lowest set bit, down to level 1
+    template <class W>
+    __device__ __forceinline__ static void descend(W &w, u32 i)
+    {
+        if (i == 0u) {
+            for (int s = LOGN - 1; s >= 1; s--) node<false>(w, s);
+        } else {
+            const int t = __builtin_ctz(i);
+            node<true>(w, t);
+            for (int s = t - 1; s >= 1; s--) node<false>(w, s);
+        }
+    }
+};
+
+// L = 16 or 32: two dwords per index word, T = two copies of {pm, a_lo, a_hi, b_lo, b_hi, bit}[L]
+template <int LOGN, int L>
+struct Wide {
+    typedef u64 Word;
+    static constexpr int FB = 5;
+    static constexpr int WORD_DW = 2;
+    static constexpr int A_DW = (1 << LOGN) / 4;      // per physical array: levels 1 .. LOGN-2 (dword 0 unused)
+    static constexpr int TOP_LEVEL = LOGN - 2;
+    // waves per block: 4 where four fit the 64 KB of a block's static LDS, else as many as fit
+    static constexpr int wpb(int wave_dw) { return 16384 / wave_dw >= 4 ? 4 : 16384 / wave_dw; }
+    static_assert(LOGN >= 5 && LOGN <= 10 && (L == 16 || L == 32), "N = 32 .. 1024, 16 or 32 paths");
+
+    __device__ __forceinline__ static Word load(const u32 *t, u32 r) { return (u64)t[r] | ((u64)t[L + r] << 32); }
+    __device__ __forceinline__ static void store(u32 *t, u32 r, Word w)
+    {
+        t[r] = (u32)w;
+        t[L + r] = (u32)(w >> 32);
+    }
+
+    // how a node step gets level s + 1: from the arrays, or (s = LOGN - 2) from the channel by F or G
+    enum Top { STORED = 0, TOP_F = 1, TOP_G = 2 };
+
+    // LLR pair x (0 <= x < N/4) of the virtual level LOGN - 1 of the path whose word b is ib
+    template <int TOPK, class W>
+    __device__ __forceinline__ static u32 top_pair(W &w, int x, u64 ib)
+    {
+        typedef typename W::S S;
+        const u32 ra = w.R[x], rb = w.R[x + S::N / 4];
+        if (TOPK == TOP_F) return f_pk(ra, rb);
+        const u32 q = W::field(ib, LOGN - 1);
+        return g_pk(ra, rb, w.B[q * S::B_DW + boff(LOGN - 1) + (x >> 4)] >> ((2 * x) & 31));
+    }
+
+    // level s (1 <= s <= LOGN - 2) of every live path from level s + 1: count * 2^(s-1) LLR pairs
+    // over the 64 lanes. F reads the path's own array (written by the step before), G the array the
+    // index word names and the partial sums of its left child; TOPK != STORED (s = LOGN - 2 only)
+    // takes level s + 1 from the channel instead.
+    template <bool IS_G, int TOPK, class W>
+    __device__ __forceinline__ static void node(W &w, int s)
+    {
+        typedef typename W::S S;
+        const int sh = s - 1, half = 1 << sh, total = w.count << sh;
+        for (int x = (int)w.lane; x < total; x += 64) {
+            const int j = x >> sh, e = x & (half - 1);
+            const u64 ib = (IS_G || TOPK == TOP_G) ? w.word_b(w.cur, j) : 0ull;
+            u32 a, b, u = 0;
+            if (TOPK == STORED) {
+                const u32 p = IS_G ? W::field(w.word_a(w.cur, j), s + 1) : (u32)j;
+                const u32 *in = w.A + p * S::A_DW + (1 << s);
+                a = in[e];
+                b = in[e + half];
+            } else {
+                a = top_pair<TOPK>(w, e, ib);
+                b = top_pair<TOPK>(w, e + half, ib);
+            }
+            if (IS_G) u = w.B[W::field(ib, s) * S::B_DW + boff(s) + (e >> 4)] >> ((2 * e) & 31);
+            w.A[j * S::A_DW + half + e] = IS_G ? g_pk(a, b, u) : f_pk(a, b);
+        }
+        wave_phase();
+    }
+
+    // the levels leaf i (even) needs below its lowest set bit, down to level 1
+    template <class W>
+    __device__ __forceinline__ static void descend(W &w, u32 i)
+    {
+        typedef typename W::S S;
+        int t;
+        if (i == 0u) {
+            node<false, TOP_F>(w, TOP_LEVEL);
+            t = TOP_LEVEL;
+        } else {
+            t = __builtin_ctz(i);
+            if (t == LOGN - 1) {          // i = N/2: G of the virtual level, then F
+                node<false, TOP_G>(w, TOP_LEVEL);
+                t = TOP_LEVEL;
+            } else if (t == TOP_LEVEL) {  // i = N/4 or 3N/4
+                if (i < (u32)S::N / 2u) node<true, TOP_F>(w, TOP_LEVEL);
+                else node<true, TOP_G>(w, TOP_LEVEL);
+            } else {
+                node<true, STORED>(w, t);
+            }
+        }
+        for (int s = t - 1; s >= 1; s--) node<false, STORED>(w, s);
+    }
+};
+
+template <int LOGN, int L>
+struct Shape {
+    typedef std::conditional_t<(L <= 8), Narrow<LOGN, L>, Wide<LOGN, L>> Lay;
+    static constexpr int N = 1 << LOGN;
+    static constexpr int D = N / 32;                  // dwords of a codeword
+    static constexpr int R_DW = N / 2;                // channel LLRs, int16
+    static constexpr int A_DW = Lay::A_DW;
+    static constexpr int B_DW = boff(LOGN) + D;       // levels 0 .. LOGN
+    static constexpr int T_ROW = 2 + 2 * Lay::WORD_DW;      // dwords per rank: pm, word a, word b, bit
+    static constexpr int T_DW = 2 * T_ROW * L;        // two copies
+    static constexpr int WAVE_DW = R_DW + L * A_DW + L * B_DW + T_DW;
+    static constexpr int WPB = Lay::wpb(WAVE_DW);
+    static constexpr int IROW = D < 2 ? 2 : D;        // information-row image per path (dwords), inside A
+    static_assert(WPB >= 1, "a wave's state fits a block's static LDS");
+    static_assert(IROW <= A_DW, "the information image reuses the LLR arrays");
+    static_assert(Lay::FB * LOGN <= 32 * Lay::WORD_DW, "a field per level in an index word");
+};
+
+// a 1 in every whole field of an index word
+template <class Word, int FB>
+__host__ __device__ constexpr Word field_ones()
 {
-    const uint4 *q = (const uint4 *)(tab + d);
-    const uint4 a = q[0], b = q[1];
-    Ent e;
-    e.m = a.x; e.off = a.y; e.mv[0] = a.z; e.mv[1] = a.w;
-    e.mv[2] = b.x; e.mv[3] = b.y; e.mv[4] = b.z; e.pc = b.w;
-    return e;
+    Word w = 0;
+    for (int k = 0; k < (int)(8 * sizeof(Word)) / FB; k++) w |= (Word)1 << (FB * k);
+    return w;
 }
 
 // The state of one frame; every member function is called by the whole wave.
 template <int LOGN, int L>
 struct Wave {
     typedef Shape<LOGN, L> S;
+    typedef typename S::Lay Lay;
+    typedef typename Lay::Word Word;
+    static constexpr int FB = Lay::FB, ROW = S::T_ROW * L;      // ROW: dwords of a copy of T
     u32 *R, *A, *B, *T;
     u32 lane;
     int count;      // live paths (wave-uniform)
     int cur;        // which copy of T is current
 
-    __device__ __forceinline__ u32 *tab_pm(int c) { return T + c * 4 * L; }
-    __device__ __forceinline__ u32 *tab_a(int c) { return T + c * 4 * L + L; }
-    __device__ __forceinline__ u32 *tab_b(int c) { return T + c * 4 * L + 2 * L; }
-    __device__ __forceinline__ u32 *tab_bit(int c) { return T + c * 4 * L + 3 * L; }
+    __device__ __forceinline__ static u32 field(Word w, int s) { return (u32)(w >> (FB * s)) & ((1u << FB) - 1u); }
 
-    // level s (1 <= s < LOGN) of every live path from level s + 1: count * 2^(s-1) LLR pairs over
-    // the 64 lanes. F reads the path's own array (written by the step before) or, at the top, the
-    // channel; G reads the array the index word names and the partial sums of its left child.
-    template <bool IS_G>
-    __device__ __forceinline__ void node(int s)
+    __device__ __forceinline__ u32 *tab_pm(int c) { return T + c * ROW; }
+    __device__ __forceinline__ u32 *tab_bit(int c) { return T + c * ROW + ROW - L; }
+    __device__ __forceinline__ Word word_a(int c, u32 r) { return Lay::load(T + c * ROW + L, r); }
+    __device__ __forceinline__ Word word_b(int c, u32 r) { return Lay::load(T + c * ROW + (1 + Lay::WORD_DW) * L, r); }
+    __device__ __forceinline__ void set_words(int c, u32 r, Word a, Word b)
     {
-        const int sh = s - 1, half = 1 << sh, total = count << sh;
-        for (int w = (int)lane; w < total; w += 64) {
-            const int j = w >> sh, e = w & (half - 1);
-            const u32 *in;
-            u32 u = 0;
-            if (s + 1 == LOGN) {
-                in = R;
-            } else {
-                const u32 p = IS_G ? field(tab_a(cur)[j], s + 1) : (u32)j;
-                in = A + p * S::A_DW + (1 << s);
-            }
-            if (IS_G) {
-                const u32 q = field(tab_b(cur)[j], s);
-                u = B[q * S::B_DW + boff(s) + (e >> 4)] >> ((2 * e) & 31);
-            }
-            const u32 a = in[e], b = in[e + half];
-            A[j * S::A_DW + half + e] = IS_G ? g_pk(a, b, u) : f_pk(a, b);
-        }
-        wave_phase();
+        Lay::store(T + c * ROW + L, r, a);
+        Lay::store(T + c * ROW + (1 + Lay::WORD_DW) * L, r, b);
     }
+
+    __device__ __forceinline__ void descend(u32 i) { Lay::descend(*this, i); }
 
     // the LLR of leaf i for path r (r < count): F or G of the level-1 pair
     __device__ __forceinline__ int leaf_llr(u32 i, u32 r)
@@ -177,8 +302,8 @@ struct Wave {
             const u32 v = A[r * S::A_DW + 1];
             return f_one((short)(v & 0xFFFFu), (short)(v >> 16));
         }
-        const u32 v = A[field(tab_a(cur)[r], 1) * S::A_DW + 1];
-        const u32 u = B[field(tab_b(cur)[r], 0) * S::B_DW] & 1u;
+        const u32 v = A[field(word_a(cur, r), 1) * S::A_DW + 1];
+        const u32 u = B[field(word_b(cur, r), 0) * S::B_DW] & 1u;
         return g_one((short)(v & 0xFFFFu), (short)(v >> 16), u);
     }
 
@@ -192,18 +317,20 @@ struct Wave {
         wave_phase();
     }
 
-    // candidates 2 r + bit in lanes 0 .. 2 count - 1; the survivors go to the other copy of T
+    // candidates 2 r + bit in lanes 0 .. 2 count - 1; the survivors go to the other copy of T. The
+    // key keeps r in FB bits (PM' < 2^25, so the key stays below the 0xFFFFFFFF of an idle lane).
     __device__ __forceinline__ void info_leaf(u32 i)
     {
         const u32 r = lane >> 1, bit = lane & 1u;
         const bool valid = (int)r < count;
-        u32 key = 0xFFFFFFFFu, pm = 0, ia = 0, ib = 0;
+        u32 key = 0xFFFFFFFFu, pm = 0;
+        Word ia = 0, ib = 0;
         if (valid) {
             const int lam = leaf_llr(i, r);
-            ia = tab_a(cur)[r];
-            ib = tab_b(cur)[r];
+            ia = word_a(cur, r);
+            ib = word_b(cur, r);
             pm = tab_pm(cur)[r] + (bit != (u32)(lam < 0) ? (u32)abs(lam) : 0u);
-            key = (pm << 4) | (r << 1) | bit;
+            key = (pm << (FB + 1)) | (r << 1) | bit;
         }
         u32 dest = 0;
 #pragma unroll
@@ -211,8 +338,7 @@ struct Wave {
         const int nxt = cur ^ 1;
         if (valid && dest < (u32)L) {
             tab_pm(nxt)[dest] = pm;
-            tab_a(nxt)[dest] = ia;
-            tab_b(nxt)[dest] = ib;
+            set_words(nxt, dest, ia, ib);
             tab_bit(nxt)[dest] = bit;
         }
         cur = nxt;
@@ -223,14 +349,15 @@ struct Wave {
     // fold the bit decided at leaf i into the partial sums: t = the level of the first ancestor that
     // is a left child (LOGN after the last leaf). Levels below 5 fold in a register of lane j =
     // rank j; higher ones in place in the destination, one dword per lane. Then rank j owns array j
-    // for that level of the partial sums and for the LLR levels 1 .. t the next leaf rewrites.
+    // for that level of the partial sums and for the stored LLR levels among 1 .. t, which the next
+    // leaf rewrites.
     __device__ __forceinline__ void fold_bits(u32 i)
     {
         const int t = (i + 1u == (u32)S::N) ? LOGN : __builtin_ctz(i + 1u);
         const bool live = (int)lane < count;
-        u32 ib = 0;
+        Word ib = 0;
         if (live) {
-            ib = tab_b(cur)[lane];
+            ib = word_b(cur, lane);
             u32 beta = tab_bit(cur)[lane];
             const int ts = t < 5 ? t : 5;
             for (int s = 0; s < ts; s++) {
@@ -246,31 +373,22 @@ struct Wave {
                 const int j = x >> sh, d = x & (w - 1);
                 u32 *dst = B + j * S::B_DW + boff(t);
                 const u32 c = dst[d];
-                dst[d] = c ^ B[field(tab_b(cur)[j], s) * S::B_DW + boff(s) + d];
+                dst[d] = c ^ B[field(word_b(cur, j), s) * S::B_DW + boff(s) + d];
                 dst[w + d] = c;
             }
             wave_phase();
         }
         if (live && t < LOGN) {
-            constexpr u32 ONES = 01111111111u;                  // a 1 in every 3-bit field
-            const u32 am = ((1u << (3 * t + 3)) - 1u) & ~7u;    // fields 1 .. t
-            tab_a(cur)[lane] = (tab_a(cur)[lane] & ~am) | ((lane * ONES) & am);
-            tab_b(cur)[lane] = (ib & ~(7u << (3 * t))) | (lane << (3 * t));
+            constexpr Word ONE = 1, FM = (ONE << FB) - ONE;             // FM: one field
+            const int ta = t < Lay::TOP_LEVEL ? t : Lay::TOP_LEVEL;
+            const Word am = ((ONE << (FB * ta + FB)) - ONE) & ~FM;      // fields 1 .. ta
+            const Word ia = word_a(cur, lane);
+            set_words(cur, lane, (ia & ~am) | (((Word)lane * field_ones<Word, FB>()) & am),
+                      (ib & ~(FM << (FB * t))) | ((Word)lane << (FB * t)));
         }
         wave_phase();
     }
 };
-
-// dwords of a codeword through u = x F^{(x)n}: the five stages inside a dword
-__device__ __forceinline__ u32 xf_dword(u32 w)
-{
-    w ^= (w >> 1) & 0x55555555u;
-    w ^= (w >> 2) & 0x33333333u;
-    w ^= (w >> 4) & 0x0F0F0F0Fu;
-    w ^= (w >> 8) & 0x00FF00FFu;
-    w ^= (w >> 16) & 0x0000FFFFu;
-    return w;
-}
 
 // CRC of the rule over an information row in LDS: register zero, no reflection, no final XOR;
 // message = bits 0 .. K-c-1 MSB first, check = bits K-c .. K-1 MSB first. One lane per path.
@@ -336,19 +454,14 @@ __global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_kern
         W.R[2 * q] = ((u32)l0 & 0xFFFFu) | ((u32)l1 << 16);
         W.R[2 * q + 1] = ((u32)l2 & 0xFFFFu) | ((u32)l3 << 16);
     }
-    if (lane < (u32)S::T_DW) W.T[lane] = 0u;         // rank 0: metric 0, every level in array 0
+    // rank 0: metric 0, every level in array 0
+    for (int x = (int)lane; x < S::T_DW; x += 64) W.T[x] = 0u;
     wave_phase();
 
     u32 mword = 0;
     for (u32 i = 0; i < (u32)N; i++) {
         if (!(i & 31u)) mword = tab[i >> 5].m;       // (uniform: a scalar load)
-        if (i == 0u) {
-            for (int s = LOGN - 1; s >= 1; s--) W.template node<false>(s);
-        } else if (!(i & 1u)) {
-            const int t = __builtin_ctz(i);
-            W.template node<true>(t);
-            for (int s = t - 1; s >= 1; s--) W.template node<false>(s);
-        }
+        if (!(i & 1u)) W.descend(i);
         if ((mword >> (i & 31u)) & 1u) W.info_leaf(i);
         else W.frozen_leaf(i);
         W.fold_bits(i);
@@ -407,70 +520,66 @@ void launch(hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, 
                            info, rank_out, idx, count);
 }
 
-template <int LOGN>
-void launch_l(int L, hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly, u32 clen,
-              u32 *info, uint8_t *rank_out, const u32 *idx, const u32 *count)
+// one instantiation: its launcher and the LDS accounting of DESIGN.md 3.11
+struct Inst {
+    decltype(&launch<5, 1>) launch;
+    uint32_t wave_dw, wpb;
+};
+
+template <int LOGN, int L>
+constexpr Inst inst() { return {launch<LOGN, L>, Shape<LOGN, L>::WAVE_DW, Shape<LOGN, L>::WPB}; }
+
+#define POLAR_LIST_ROW(LN) {inst<LN, 1>(), inst<LN, 2>(), inst<LN, 4>(), inst<LN, 8>(), inst<LN, 16>(), inst<LN, 32>()}
+const Inst INST[6][6] = {POLAR_LIST_ROW(5), POLAR_LIST_ROW(6), POLAR_LIST_ROW(7),
+                         POLAR_LIST_ROW(8), POLAR_LIST_ROW(9), POLAR_LIST_ROW(10)};
+#undef POLAR_LIST_ROW
+
+// the instantiation for N = 2^logn and L paths; null when there is none
+const Inst *find(int logn, int L)
 {
-    switch (L) {
-    case 1: launch<LOGN, 1>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    case 2: launch<LOGN, 2>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    case 4: launch<LOGN, 4>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    default: launch<LOGN, 8>(s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    }
+    if (logn < 5 || logn > 10 || L < 1 || L > 32 || (L & (L - 1))) return nullptr;
+    return &INST[logn - 5][__builtin_ctz((unsigned)L)];
 }
 
-void launch_n(uint32_t N, int L, hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly,
-              u32 clen, u32 *info, uint8_t *rank_out, const u32 *idx, const u32 *count)
+// log2 N of a power of two, else -1
+int log2_exact(uint32_t N) { return (N && !(N & (N - 1u))) ? __builtin_ctz(N) : -1; }
+
+void shape_of(const Inst *k, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block)
 {
-    switch (N) {
-    case 32: launch_l<5>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    case 64: launch_l<6>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    case 128: launch_l<7>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    case 256: launch_l<8>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    case 512: launch_l<9>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    default: launch_l<10>(L, s, tab, llr, batch, K, poly, clen, info, rank_out, idx, count); break;
-    }
+    *lds_bytes_per_wave = k ? k->wave_dw * 4u : 0u;
+    *waves_per_block = k ? k->wpb : 0u;
 }
 
 }  // namespace polar_list
 
 // tab_dev: the plan's transform table (polar_sc_xform_table). 32 <= N <= 1024 a power of two,
-// L in {1, 2, 4, 8}, 1 <= K <= N, clen = 0 (no CRC) or 1 <= clen <= 32 and < K, 1 <= batch <= 2^31 - 8.
-// Returns 0 or a hipError_t.
+// L in {1, 2, 4, 8, 16, 32}, 1 <= K <= N, clen = 0 (no CRC) or 1 <= clen <= 32 and < K,
+// 1 <= batch <= 2^31 - 8. idx_dev == NULL: every frame of the batch. Else only the frames
+// idx_dev[0 .. *count_dev) (both written earlier on `stream`; idx_dev holds `batch` entries): the
+// info_dev and rank_dev rows of the other frames are left alone. Returns 0 or a hipError_t.
 extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
                                     int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
-                                    void *stream)
+                                    const uint32_t *idx_dev, const uint32_t *count_dev, void *stream)
 {
-    polar_list::launch_n(N, L, (hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly,
-                         clen, (uint32_t *)info_dev, rank_dev, nullptr, nullptr);
+    const polar_list::Inst *k = polar_list::find(polar_list::log2_exact(N), L);
+    if (!k) return (int)hipErrorInvalidValue;
+    k->launch((hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly, clen,
+              (uint32_t *)info_dev, rank_dev, idx_dev, count_dev);
     return (int)hipGetLastError();
 }
 
-// The same decoder over the frames idx_dev[0 .. *count_dev) only (both written earlier on `stream`;
-// idx_dev holds `batch` entries): info_dev and rank_dev rows of the other frames are left alone.
-extern "C" int polar_sc_launch_list_indexed(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
-                                            uint32_t K, int L, uint32_t poly, uint32_t clen, uint64_t *info_dev,
-                                            uint8_t *rank_dev, const uint32_t *idx_dev, const uint32_t *count_dev,
-                                            void *stream)
-{
-    polar_list::launch_n(N, L, (hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly,
-                         clen, (uint32_t *)info_dev, rank_dev, idx_dev, count_dev);
-    return (int)hipGetLastError();
-}
-
-// static LDS per block and waves per block of the kernel for (N, L): the accounting of DESIGN.md 3.11
+// static LDS per wave and waves per block of the kernel for (N, L), L <= 8 (zeros otherwise): the
+// accounting of DESIGN.md 3.11
 extern "C" void polar_sc_list_shape(uint32_t N, int L, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block)
 {
-    using namespace polar_list;
     int logn = 5;
-    while ((1u << logn) < N) logn++;
-    uint32_t dw = 0, wpb = 0;
-#define POLAR_LIST_CASE(LN, LL) \
-    if (logn == LN && L == LL) dw = Shape<LN, LL>::WAVE_DW, wpb = Shape<LN, LL>::WPB;
-#define POLAR_LIST_ROW(LN) POLAR_LIST_CASE(LN, 1) POLAR_LIST_CASE(LN, 2) POLAR_LIST_CASE(LN, 4) POLAR_LIST_CASE(LN, 8)
-    POLAR_LIST_ROW(5) POLAR_LIST_ROW(6) POLAR_LIST_ROW(7) POLAR_LIST_ROW(8) POLAR_LIST_ROW(9) POLAR_LIST_ROW(10)
-#undef POLAR_LIST_ROW
-#undef POLAR_LIST_CASE
-    *lds_bytes_per_wave = dw * 4u;
-    *waves_per_block = wpb;
+    while (logn <= 10 && (1u << logn) < N) logn++;
+    polar_list::shape_of(L <= 8 ? polar_list::find(logn, L) : nullptr, lds_bytes_per_wave, waves_per_block);
+}
+
+// the same for N = 32 .. 1024 a power of two and L = 16 or 32 (zeros otherwise)
+extern "C" void polar_sc_list_wide_shape(uint32_t N, int L, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block)
+{
+    polar_list::shape_of(L >= 16 ? polar_list::find(polar_list::log2_exact(N), L) : nullptr, lds_bytes_per_wave,
+                         waves_per_block);
 }

@@ -13,45 +13,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "polar_sc_xf.h"
+
 namespace polar_xf {
-
-typedef uint32_t u32;
-
-// per-dword record of the plan's table (polar_sc_xform_table): everything the device needs to
-// know about the mask, so that it does no mask arithmetic and takes no data-dependent branch
-struct __attribute__((aligned(32))) Ent {
-    u32 m;       // mask bits of the dword (1 = information)
-    u32 off;     // information bits before this dword
-    u32 mv[5];   // move masks of the parallel-suffix compress (Hacker's Delight 7-4)
-    u32 pc;      // popcount(m)
-};
 
 constexpr int WAVES = 4;              // waves per block; each works alone
 constexpr int CHUNK = 2048;           // dwords one wave holds at most (32 registers x 64 lanes)
 
-__device__ __forceinline__ Ent load_ent(const Ent *__restrict__ tab, size_t d)
-{
-    const uint4 *q = (const uint4 *)(tab + d);
-    const uint4 a = q[0], b = q[1];
-    Ent e;
-    e.m = a.x; e.off = a.y; e.mv[0] = a.z; e.mv[1] = a.w;
-    e.mv[2] = b.x; e.mv[3] = b.y; e.mv[4] = b.z; e.pc = b.w;
-    return e;
-}
-
-// the bits of x under e.m, packed at the low end in position order
-__device__ __forceinline__ u32 compress(u32 x, const Ent &e)
-{
-    x &= e.m;
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const u32 t = x & e.mv[i];
-        x = (x ^ t) | (t >> (1 << i));
-    }
-    return x;
-}
-
-// inverse: the low popcount(m) bits of x spread to the positions of e.m
+// inverse of compress: the low popcount(m) bits of x spread to the positions of e.m
 __device__ __forceinline__ u32 expand(u32 x, const Ent &e)
 {
 #pragma unroll
@@ -60,17 +29,6 @@ __device__ __forceinline__ u32 expand(u32 x, const Ent &e)
         x = (x & ~e.mv[i]) | (t & e.mv[i]);
     }
     return x & e.m;
-}
-
-// stages of bit distance 1..16: bit j with the distance bit clear takes bit j + h
-__device__ __forceinline__ u32 xf_dword(u32 w)
-{
-    w ^= (w >> 1) & 0x55555555u;
-    w ^= (w >> 2) & 0x33333333u;
-    w ^= (w >> 4) & 0x0F0F0F0Fu;
-    w ^= (w >> 8) & 0x00FF00FFu;
-    w ^= (w >> 16) & 0x0000FFFFu;
-    return w;
 }
 
 // one stage between lanes: the lane with the distance bit clear takes w ^= w of lane + DIST;
@@ -130,15 +88,6 @@ __device__ __forceinline__ void scatter_info(u32 *seg, u32 q0, u32 c, const Ent 
     const u32 sh = e.off & 31u, q = (e.off >> 5) - q0;
     if (e.pc) atomicOr(&seg[q], c << sh);
     if (sh + e.pc > 32u) atomicOr(&seg[q + 1], c >> (32u - sh));   // (sh > 0 here)
-}
-
-// orders the phases of a wave's LDS image (clear, OR, read): LDS executes one wave's
-// instructions in order, so only the compiler has to be held
-__device__ __forceinline__ void wave_phase()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---------------------------------------------------------------------------------------
