@@ -424,6 +424,30 @@ int polar_sc_decode_list_wide_to_info(const polar_sc_plan *plan, const int8_t *l
  * (a power of two) and list_size 16 or 32; zeros for anything else. Host only. */
 void polar_sc_list_wide_shape(uint32_t N, int list_size, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block);
 
+/* ---- Convolutionally precoded (PAC) codes, N <= 1024 ("Precoded codes") ----
+ * A rate-1 convolutional precoder ahead of the polar transform; any polar code whose dynamic frozen
+ * bits are a sliding-window parity of earlier bits is this. conv_len = 1 .. 32 taps, bit j of conv_poly
+ * = c_j for 0 <= j < conv_len, c_0 = c_{conv_len-1} = 1 and conv_poly < 2^conv_len (-EINVAL otherwise).
+ * (1, 1) is the identity; the usual PAC precoder 133 octal is (0x6D, 7). With v = the information bits
+ * at the information positions of the plan's mask and 0 at the frozen ones, the transmitted word is
+ * u_i = XOR_{j <= min(i, conv_len-1)} c_j v_{i-j}, x = u . F^{(x)n}. */
+
+/* polar_sc_decode_list_wide_to_info for such a code: list_size in {1, 2, 4, 8, 16, 32}, the same
+ * arguments, CRC rule, results and error codes. Every path carries its last conv_len - 1 values of v;
+ * a frozen position decides u_i = feed_i (its metric adds |llr| when that disagrees with the sign), an
+ * information position forks on the data bit v_i, u_i = v_i ^ feed_i, and candidates are ordered by
+ * (metric, rank, v_i). info_dev receives v at the information positions; the CRC runs over those bits.
+ * With (1, 1) every frame gives what polar_sc_decode_list_wide_to_info gives. One launch of the list
+ * kernel's precoded variant; nothing allocated after the first call or polar_sc_plan_prepare. */
+int polar_sc_decode_list_precoded_to_info(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch,
+                                          int list_size, uint32_t conv_poly, int conv_len, uint32_t crc_poly,
+                                          int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream);
+
+/* polar_sc_encode for such a code (its arguments and rows): expand by the mask, precode on packed
+ * bits, transform; one launch. -ENOTSUP: N > 1024. */
+int polar_sc_encode_precoded(const polar_sc_plan *plan, const uint64_t *info_dev, uint64_t *x_dev, size_t batch,
+                             uint32_t conv_poly, int conv_len, void *stream);
+
 /* ---- Adaptive CRC-aided decoding, N <= 1024 ----
  * Successive cancellation first, the list decoder only for the frames whose SC result fails the
  * CRC, in one asynchronous call with no host round trip. The CRC is that of

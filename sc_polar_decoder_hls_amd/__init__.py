@@ -132,6 +132,7 @@ EXPORTS = (
     "polar_sc_quantize", "polar_sc_soft_info_get", "polar_sc_decode_soft",
     "polar_sc_to_info_get", "polar_sc_decode_to_info", "polar_sc_decode_soft_to_info",
     "polar_sc_decode_list_to_info", "polar_sc_decode_list_wide_to_info",
+    "polar_sc_decode_list_precoded_to_info", "polar_sc_encode_precoded",
     "polar_sc_crc_check", "polar_sc_adaptive_workspace", "polar_sc_decode_adaptive_to_info",
     "polar_sc_decode_adaptive_wide_to_info",
 )
@@ -186,6 +187,8 @@ def lib():
         "polar_sc_list_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
         "polar_sc_decode_list_wide_to_info": [p, p, sz, i32, u32, i32, p, p, p],
         "polar_sc_decode_adaptive_wide_to_info": [p, p, sz, i32, u32, i32, p, p, p, p, p],
+        "polar_sc_decode_list_precoded_to_info": [p, p, sz, i32, u32, i32, u32, i32, p, p, p],
+        "polar_sc_encode_precoded": [p, p, p, sz, u32, i32, p],
         "polar_sc_list_wide_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
@@ -652,7 +655,7 @@ class Decoder:
         return out
 
     # -- list decoding ------------------------------------------------------------
-    def decode_list(self, llr, list_size, crc=None, out=None, rank=None, stream=None):
+    def decode_list(self, llr, list_size, crc=None, out=None, rank=None, stream=None, precode=None):
         """Successive-cancellation list decoding of int8 LLRs [B, N] (N <= 1024) with `list_size`
         paths (1, 2, 4, 8, 16 or 32; 16 and 32 run the wide-list kernel, through
         polar_sc_decode_list_wide_to_info): returns (info, rank), the information words [B, info_words] of
@@ -660,7 +663,11 @@ class Decoder:
         crc: None (the best path, rank 0) or (poly, length): the last `length` information bits are
         the CRC crc_attach() appends; the lowest rank that passes is chosen, rank 0 and 255 in
         `rank` when none does. list_size = 1 is successive cancellation in the list decoder's own
-        arithmetic (G clamped at +-32767), not bit-equal to decode(). Asynchronous on `stream`."""
+        arithmetic (G clamped at +-32767), not bit-equal to decode(). Asynchronous on `stream`.
+        precode: None, or (conv_poly, conv_len) for a convolutionally precoded (PAC) code as
+        encode(precode=...) sends it (polar_sc_decode_list_precoded_to_info): bit j of conv_poly is tap
+        c_j, 1 <= conv_len <= 32, first and last tap set; `info` then holds the data bits v, and (1, 1)
+        gives what None gives."""
         torch = self._check_llr(llr)
         B = llr.shape[0]
         poly, length = (0, 0) if crc is None else (int(crc[0]), int(crc[1]))
@@ -675,8 +682,11 @@ class Decoder:
         with torch.cuda.device(llr.device):
             s = stream if stream is not None else torch.cuda.current_stream(llr.device)
             fn = "polar_sc_decode_list_wide_to_info" if int(list_size) in (16, 32) else "polar_sc_decode_list_to_info"
+            conv = ()
+            if precode is not None:
+                fn, conv = "polar_sc_decode_list_precoded_to_info", (int(precode[0]), int(precode[1]))
             _check(fn, getattr(lib(), fn)(
-                self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), poly, length,
+                self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(list_size), *conv, poly, length,
                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
         return out, rank
 
@@ -751,7 +761,7 @@ class Decoder:
         return out, rank, stage
 
     # -- information bits on the device ----------------------------------------
-    def _xform(self, fn, src, cols_in, cols_out, out, stream, name):
+    def _xform(self, fn, src, cols_in, cols_out, out, stream, name, extra=()):
         torch = _torch()
         if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.int64):
             raise TypeError("%s must be a CUDA int64 tensor" % name)
@@ -767,7 +777,7 @@ class Decoder:
         with torch.cuda.device(src.device):
             s = stream if stream is not None else torch.cuda.current_stream(src.device)
             _check(fn, getattr(lib(), fn)(self._plan, ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(out.data_ptr()), B,
-                                          ctypes.c_void_p(s.cuda_stream)))
+                                          *extra, ctypes.c_void_p(s.cuda_stream)))
         return out
 
     def extract_info(self, xhat, out=None, stream=None):
@@ -777,10 +787,15 @@ class Decoder:
         Asynchronous on `stream`."""
         return self._xform("polar_sc_extract_info", xhat, self.words, self.info_words, out, stream, "xhat")
 
-    def encode(self, info, out=None, stream=None):
+    def encode(self, info, out=None, stream=None, precode=None):
         """The inverse: information words [B, info_words] -> codeword words [B, ceil(N/64)] (frozen
-        bits zero; bits of `info` at and above K are ignored)."""
-        return self._xform("polar_sc_encode", info, self.info_words, self.words, out, stream, "info")
+        bits zero; bits of `info` at and above K are ignored). precode: None, or (conv_poly, conv_len):
+        the convolutional precoder of decode_list(precode=...) between the mask and the transform
+        (polar_sc_encode_precoded, N <= 1024)."""
+        if precode is None:
+            return self._xform("polar_sc_encode", info, self.info_words, self.words, out, stream, "info")
+        return self._xform("polar_sc_encode_precoded", info, self.info_words, self.words, out, stream, "info",
+                           (int(precode[0]), int(precode[1])))
 
     def decode_info(self, llr, out=None, xhat=None, stream=None):
         """decode() followed by extract_info() on the same stream: int8 LLRs [B, N] -> information

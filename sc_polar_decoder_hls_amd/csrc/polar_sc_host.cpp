@@ -37,6 +37,12 @@ extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stre
 extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, uint32_t K,
                                     int L, uint32_t poly, uint32_t clen, uint64_t *info_dev, uint8_t *rank_dev,
                                     const uint32_t *idx_dev, const uint32_t *count_dev, void *stream);
+// the same kernel and the encoder for a convolutionally precoded code (conv_poly: bit j = c_j, c_0 = 1)
+extern "C" int polar_sc_launch_list_precoded(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
+                                             uint32_t K, int L, uint32_t conv_poly, uint32_t poly, uint32_t clen,
+                                             uint64_t *info_dev, uint8_t *rank_dev, void *stream);
+extern "C" int polar_sc_launch_encode_precoded(const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev, uint32_t N,
+                                               uint32_t K, size_t batch, uint32_t conv_poly, void *stream);
 extern "C" size_t polar_sc_crc_table_dwords(uint32_t K, uint32_t c);
 extern "C" void polar_sc_crc_table(uint32_t K, uint32_t poly, uint32_t c, uint32_t *tab);
 extern "C" int polar_sc_launch_crc_check(const void *tab_dev, const uint64_t *info_dev, size_t batch, uint32_t K,
@@ -1413,12 +1419,22 @@ int polar_sc_decode_soft_to_info(const polar_sc_plan *p, const void *v_dev, int 
 }
 
 namespace {
-// the one body of the list entries: max_list = 8 (the narrow layout only) or 32
+// a precoder of the rule: 1 <= conv_len <= 32 taps, the first and the last one set,
+// none above them
+bool conv_args_ok(uint32_t conv_poly, int conv_len)
+{
+    return conv_len >= 1 && conv_len <= 32 && (conv_poly & 1u) && (conv_poly >> (conv_len - 1)) == 1u;
+}
+
+// the one body of the list entries: max_list = 8 (the narrow layout only) or 32; conv_len = 0: the
+// plain code, else the code precoded with (conv_poly, conv_len)
 int list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size, int max_list,
-                 uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
+                 uint32_t conv_poly, int conv_len, uint32_t crc_poly, int crc_len, uint64_t *info_dev,
+                 uint8_t *rank_dev, void *stream)
 {
     if (!p) return -EINVAL;
     if (list_size < 1 || list_size > max_list || (list_size & (list_size - 1))) return -EINVAL;
+    if (conv_len && !conv_args_ok(conv_poly, conv_len)) return -EINVAL;
     if (crc_len < 0 || crc_len > 32 || (crc_len == 0 && crc_poly != 0)) return -EINVAL;
     if (crc_len > 0 && crc_len < 32 && (crc_poly >> crc_len) != 0) return -EINVAL;
     if (crc_len > 0 && (uint32_t)crc_len >= p->K) return -EINVAL;
@@ -1428,8 +1444,10 @@ int list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, in
     if (batch > (size_t)0x7FFFFFF8) return -EINVAL;
     const void *tab = nullptr;
     if (const int e = ensure_xform(p, &tab)) return e;
-    const int rc = polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
-                                        info_dev, rank_dev, nullptr, nullptr, stream);
+    const int rc = conv_len ? polar_sc_launch_list_precoded(tab, llr_dev, batch, p->N, p->K, list_size, conv_poly, crc_poly,
+                                                            (uint32_t)crc_len, info_dev, rank_dev, stream)
+                            : polar_sc_launch_list(tab, llr_dev, batch, p->N, p->K, list_size, crc_poly, (uint32_t)crc_len,
+                                                   info_dev, rank_dev, nullptr, nullptr, stream);
     return rc ? hip_fail("list decode launch", (hipError_t)rc) : 0;
 }
 }  // namespace
@@ -1437,14 +1455,39 @@ int list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, in
 int polar_sc_decode_list_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
                                  uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev, void *stream)
 {
-    return list_to_info(p, llr_dev, batch, list_size, 8, crc_poly, crc_len, info_dev, rank_dev, stream);
+    return list_to_info(p, llr_dev, batch, list_size, 8, 0, 0, crc_poly, crc_len, info_dev, rank_dev, stream);
 }
 
 int polar_sc_decode_list_wide_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
                                       uint32_t crc_poly, int crc_len, uint64_t *info_dev, uint8_t *rank_dev,
                                       void *stream)
 {
-    return list_to_info(p, llr_dev, batch, list_size, 32, crc_poly, crc_len, info_dev, rank_dev, stream);
+    return list_to_info(p, llr_dev, batch, list_size, 32, 0, 0, crc_poly, crc_len, info_dev, rank_dev, stream);
+}
+
+int polar_sc_decode_list_precoded_to_info(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int list_size,
+                                          uint32_t conv_poly, int conv_len, uint32_t crc_poly, int crc_len,
+                                          uint64_t *info_dev, uint8_t *rank_dev, void *stream)
+{
+    if (conv_len == 0) return -EINVAL;   // (0 is list_to_info's word for "no precoder", not the caller's)
+    return list_to_info(p, llr_dev, batch, list_size, 32, conv_poly, conv_len, crc_poly, crc_len, info_dev, rank_dev,
+                        stream);
+}
+
+int polar_sc_encode_precoded(const polar_sc_plan *p, const uint64_t *info_dev, uint64_t *x_dev, size_t batch,
+                             uint32_t conv_poly, int conv_len, void *stream)
+{
+    if (!p || !conv_args_ok(conv_poly, conv_len)) return -EINVAL;
+    if (p->N > 1024u) return -ENOTSUP;
+    if (p->K == 0) return xform_common(p, 1, info_dev, x_dev, batch, stream);   // v = 0 gives u = 0: polar_sc_encode's case
+    if (batch > 0 && (!info_dev || !x_dev)) return -EINVAL;
+    if (batch == 0) return 0;
+    if (batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    const void *tab = nullptr;
+    if (const int e = ensure_xform(p, &tab)) return e;
+    const int rc = polar_sc_launch_encode_precoded(tab, info_dev, x_dev, p->N, p->K, batch, conv_poly, stream);
+    if (rc < 0) return -EINVAL;
+    return rc ? hip_fail("precoded encode launch", (hipError_t)rc) : 0;
 }
 
 // ---- adaptive CRC-aided decoding (include/polar_sc.h) -----------------------------

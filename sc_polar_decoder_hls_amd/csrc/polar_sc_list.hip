@@ -8,7 +8,8 @@
 //   R        the channel LLRs as int16 (level LOGN of the tree, shared by every path)
 //   A[p][s]  LLR arrays: level s (a node of 2^s LLRs) of physical array p, int16, at element 2^s
 //   B[p][s]  partial sums of the completed left child at level s of physical array p, bit-packed
-//   T        per rank: path metric, the two index words below, the bit decided last; in two copies
+//   T        per rank: path metric, the two index words below, the bit decided last (PRECODED: with
+//            the path's precoder history in the same dword); in two copies
 // Paths share arrays through two index words per rank, a field per level: word `a` names the
 // physical array that holds the path's LLRs of each level, word `b` the same for the partial sums.
 // Every live path walks the tree in lockstep, so a level is rewritten by all paths at once: what
@@ -36,6 +37,13 @@
 // pairs in registers from R. For leaves below N/2 the level is F(R[e], R[e + N/2]), the same for
 // every path; from N/2 on it is G(R[e], R[e + N/2], beta) with beta the path's level-(LOGN-1)
 // partial sums, found through index word b.
+//
+// PRECODED ("Precoded codes"): the code has a convolutional precoder ahead of the
+// polar transform, u_i = v_i ^ feed_i with feed_i a parity over the path's last conv_len - 1 values of
+// v. The tree, the metric and the partial sums work on u as before; a frozen leaf decides u = feed
+// (v = 0), an information leaf forks on v. The history h rides in the dword of T that holds the
+// decided bit: bits 0 .. 30 = h (bit j - 1 = v_{i-j}), bit 31 = the u decided last. The epilogue turns
+// each path's u into v before the compress by the mask.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -270,7 +278,7 @@ __host__ __device__ constexpr Word field_ones()
 }
 
 // The state of one frame; every member function is called by the whole wave.
-template <int LOGN, int L>
+template <int LOGN, int L, bool PRECODED>
 struct Wave {
     typedef Shape<LOGN, L> S;
     typedef typename S::Lay Lay;
@@ -280,6 +288,13 @@ struct Wave {
     u32 lane;
     int count;      // live paths (wave-uniform)
     int cur;        // which copy of T is current
+    u32 cmask;      // PRECODED: conv_poly >> 1, the taps on the history (bit j - 1 = c_j)
+
+    static constexpr u32 HMASK = 0x7FFFFFFFu;       // PRECODED: the history bits of a tab_bit dword
+    // the u that precoding makes of data bit v on a path whose tab_bit dword is hw
+    __device__ __forceinline__ u32 precode(u32 hw, u32 v) const { return v ^ ((u32)__builtin_popcount(hw & cmask) & 1u); }
+    // the tab_bit dword after a position that decided data bit v, sent as u
+    __device__ __forceinline__ static u32 advance(u32 hw, u32 v, u32 u) { return (u << 31) | ((hw << 1) & HMASK) | v; }
 
     __device__ __forceinline__ static u32 field(Word w, int s) { return (u32)(w >> (FB * s)) & ((1u << FB) - 1u); }
 
@@ -311,25 +326,36 @@ struct Wave {
     {
         if ((int)lane < count) {
             const int lam = leaf_llr(i, lane);
-            tab_pm(cur)[lane] += lam < 0 ? (u32)(-lam) : 0u;
-            tab_bit(cur)[lane] = 0u;
+            if constexpr (PRECODED) {
+                const u32 hw = tab_bit(cur)[lane], u = precode(hw, 0u);
+                tab_pm(cur)[lane] += u != (u32)(lam < 0) ? (u32)abs(lam) : 0u;
+                tab_bit(cur)[lane] = advance(hw, 0u, u);
+            } else {
+                tab_pm(cur)[lane] += lam < 0 ? (u32)(-lam) : 0u;
+                tab_bit(cur)[lane] = 0u;
+            }
         }
         wave_phase();
     }
 
     // candidates 2 r + bit in lanes 0 .. 2 count - 1; the survivors go to the other copy of T. The
     // key keeps r in FB bits (PM' < 2^25, so the key stays below the 0xFFFFFFFF of an idle lane).
+    // PRECODED: `bit` is the data bit v, which the key and the history take; the metric judges u.
     __device__ __forceinline__ void info_leaf(u32 i)
     {
         const u32 r = lane >> 1, bit = lane & 1u;
         const bool valid = (int)r < count;
-        u32 key = 0xFFFFFFFFu, pm = 0;
+        u32 key = 0xFFFFFFFFu, pm = 0, hw = 0, u = bit;
         Word ia = 0, ib = 0;
         if (valid) {
             const int lam = leaf_llr(i, r);
             ia = word_a(cur, r);
             ib = word_b(cur, r);
-            pm = tab_pm(cur)[r] + (bit != (u32)(lam < 0) ? (u32)abs(lam) : 0u);
+            if constexpr (PRECODED) {
+                hw = tab_bit(cur)[r];
+                u = precode(hw, bit);
+            }
+            pm = tab_pm(cur)[r] + (u != (u32)(lam < 0) ? (u32)abs(lam) : 0u);
             key = (pm << (FB + 1)) | (r << 1) | bit;
         }
         u32 dest = 0;
@@ -339,7 +365,7 @@ struct Wave {
         if (valid && dest < (u32)L) {
             tab_pm(nxt)[dest] = pm;
             set_words(nxt, dest, ia, ib);
-            tab_bit(nxt)[dest] = bit;
+            tab_bit(nxt)[dest] = PRECODED ? advance(hw, bit, u) : bit;
         }
         cur = nxt;
         count = min(L, 2 * count);
@@ -358,7 +384,7 @@ struct Wave {
         Word ib = 0;
         if (live) {
             ib = word_b(cur, lane);
-            u32 beta = tab_bit(cur)[lane];
+            u32 beta = PRECODED ? tab_bit(cur)[lane] >> 31 : tab_bit(cur)[lane];
             const int ts = t < 5 ? t : 5;
             for (int s = 0; s < ts; s++) {
                 const u32 bl = B[field(ib, s) * S::B_DW + s];
@@ -417,12 +443,14 @@ __device__ __forceinline__ bool crc_passes(const u32 *row, u32 K, u32 poly, u32 
 // stream). The grid still has a wave slot per frame of the batch; slot s decodes frame idx[s], and a
 // slot at or past the count returns before any other load. An entry outside the batch is skipped, so
 // that nothing a wrong list holds can be used as an address.
-template <int LOGN, int L, bool INDEXED>
+// PRECODED: the code is precoded with the taps cmask = conv_poly >> 1 (0: the identity); direct only.
+template <int LOGN, int L, bool INDEXED, bool PRECODED>
 __global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_kernel(
     const Ent *__restrict__ tab, const int8_t *__restrict__ llr, u32 batch, u32 K, u32 poly, u32 clen,
     u32 *__restrict__ info, uint8_t *__restrict__ rank_out, const u32 *__restrict__ idx,
-    const u32 *__restrict__ idx_count)
+    const u32 *__restrict__ idx_count, u32 cmask)
 {
+    static_assert(!(INDEXED && PRECODED), "adaptive decoding has no precoded form");
     typedef Shape<LOGN, L> S;
     constexpr int N = S::N;
     __shared__ u32 lds[S::WPB * S::WAVE_DW];
@@ -436,7 +464,8 @@ __global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_kern
         if (frame >= batch) return;
     }
 
-    Wave<LOGN, L> W;
+    Wave<LOGN, L, PRECODED> W;
+    W.cmask = cmask;
     W.R = lds + wave * S::WAVE_DW;
     W.A = W.R + S::R_DW;
     W.B = W.A + L * S::A_DW;
@@ -485,6 +514,26 @@ __global__ void __launch_bounds__((64 * Shape<LOGN, L>::WPB)) polar_sc_list_kern
         }
         wave_phase();
     }
+    if constexpr (PRECODED) {
+        // that array is the path's u: v_i = u_i ^ feed_i, where feed_i needs the v before it. One lane
+        // per path, bit-serial through the row with the leaves' own history register.
+        if ((int)lane < count) {
+            u32 *row = W.B + lane * S::B_DW + boff(LOGN);
+            u32 hw = 0;
+            for (int d = 0; d < D; d++) {
+                const u32 uw = row[d];
+                u32 vw = 0;
+#pragma unroll
+                for (int k = 0; k < 32; k++) {
+                    const u32 v = W.precode(hw, (uw >> k) & 1u);    // (the XOR with feed is its own inverse)
+                    hw = (hw << 1) | v;     // (bit 31 is no tap)
+                    vw |= v << k;
+                }
+                row[d] = vw;
+            }
+        }
+        wave_phase();
+    }
     for (int x = (int)lane; x < count * D; x += 64) {
         const int j = x / D, d = x % D;
         const Ent e = load_ent(tab, (u32)d);
@@ -513,21 +562,36 @@ void launch(hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, 
     constexpr int WPB = Shape<LOGN, L>::WPB;
     const dim3 blocks((unsigned)(((size_t)batch + WPB - 1) / WPB)), threads(64 * WPB);
     if (idx)
-        hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, true>), blocks, threads, 0, s, tab, llr, batch, K, poly, clen,
-                           info, rank_out, idx, count);
+        hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, true, false>), blocks, threads, 0, s, tab, llr, batch, K, poly,
+                           clen, info, rank_out, idx, count, 0u);
     else
-        hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, false>), blocks, threads, 0, s, tab, llr, batch, K, poly, clen,
-                           info, rank_out, idx, count);
+        hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, false, false>), blocks, threads, 0, s, tab, llr, batch, K, poly,
+                           clen, info, rank_out, idx, count, 0u);
 }
 
-// one instantiation: its launcher and the LDS accounting of DESIGN.md 3.11
+// the direct kernel of a code precoded with the taps cmask
+template <int LOGN, int L>
+void launch_precoded(hipStream_t s, const Ent *tab, const int8_t *llr, u32 batch, u32 K, u32 poly, u32 clen, u32 *info,
+                     uint8_t *rank_out, u32 cmask)
+{
+    constexpr int WPB = Shape<LOGN, L>::WPB;
+    const dim3 blocks((unsigned)(((size_t)batch + WPB - 1) / WPB)), threads(64 * WPB);
+    hipLaunchKernelGGL((polar_sc_list_kernel<LOGN, L, false, true>), blocks, threads, 0, s, tab, llr, batch, K, poly, clen,
+                       info, rank_out, (const u32 *)nullptr, (const u32 *)nullptr, cmask);
+}
+
+// one instantiation: its launchers and the LDS accounting of DESIGN.md 3.11 (the same for both)
 struct Inst {
     decltype(&launch<5, 1>) launch;
+    decltype(&launch_precoded<5, 1>) launch_precoded;
     uint32_t wave_dw, wpb;
 };
 
 template <int LOGN, int L>
-constexpr Inst inst() { return {launch<LOGN, L>, Shape<LOGN, L>::WAVE_DW, Shape<LOGN, L>::WPB}; }
+constexpr Inst inst()
+{
+    return {launch<LOGN, L>, launch_precoded<LOGN, L>, Shape<LOGN, L>::WAVE_DW, Shape<LOGN, L>::WPB};
+}
 
 #define POLAR_LIST_ROW(LN) {inst<LN, 1>(), inst<LN, 2>(), inst<LN, 4>(), inst<LN, 8>(), inst<LN, 16>(), inst<LN, 32>()}
 const Inst INST[6][6] = {POLAR_LIST_ROW(5), POLAR_LIST_ROW(6), POLAR_LIST_ROW(7),
@@ -565,6 +629,19 @@ extern "C" int polar_sc_launch_list(const void *tab_dev, const int8_t *llr_dev, 
     if (!k) return (int)hipErrorInvalidValue;
     k->launch((hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly, clen,
               (uint32_t *)info_dev, rank_dev, idx_dev, count_dev);
+    return (int)hipGetLastError();
+}
+
+// The direct launch for a precoded code: conv_poly bit j = c_j, c_0 = 1 (judged by the
+// caller), so the taps on the history are conv_poly >> 1. Everything else as polar_sc_launch_list.
+extern "C" int polar_sc_launch_list_precoded(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N,
+                                             uint32_t K, int L, uint32_t conv_poly, uint32_t poly, uint32_t clen,
+                                             uint64_t *info_dev, uint8_t *rank_dev, void *stream)
+{
+    const polar_list::Inst *k = polar_list::find(polar_list::log2_exact(N), L);
+    if (!k) return (int)hipErrorInvalidValue;
+    k->launch_precoded((hipStream_t)stream, (const polar_list::Ent *)tab_dev, llr_dev, (uint32_t)batch, K, poly, clen,
+                       (uint32_t *)info_dev, rank_dev, conv_poly >> 1);
     return (int)hipGetLastError();
 }
 

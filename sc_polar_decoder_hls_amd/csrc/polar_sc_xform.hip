@@ -130,6 +130,37 @@ __global__ void __launch_bounds__(64 * WAVES) polar_sc_xform_small_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
+// Precoded encoding, N <= 1024 (the list decoder's range; DESIGN.md 3.11 "Precoded codes"): the
+// encode path above with the convolutional precoder between the expand and the transform. v = the
+// expanded information bits, u_i = XOR over the taps c_j of v_{i-j}: on packed bits, dword d of u is
+// the XOR over the taps of {v[d], v[d-1]} shifted by j, and v[d-1] is the lane below (conv_len <= 32,
+// so no tap reaches further). cpoly: bit j = c_j, c_0 = 1.
+// ---------------------------------------------------------------------------------------
+template <int LOGD>
+__global__ void __launch_bounds__(64 * WAVES) polar_sc_encode_precoded_kernel(
+    const Ent *__restrict__ tab, const u32 *__restrict__ in, u32 *__restrict__ out, u32 batch, u32 irow, u32 cpoly)
+{
+    constexpr int D = 1 << LOGD, XROW = D < 2 ? 2 : D;
+    const size_t gl = (size_t)blockIdx.x * (64u * WAVES) + threadIdx.x;
+    const size_t frame = gl >> LOGD;
+    const u32 d = (u32)gl & (u32)(D - 1), lane = threadIdx.x & 63u;
+    const bool valid = frame < batch;
+    const Ent e = load_ent(tab, d);
+    const u32 v = expand(valid ? gather_info(in + frame * irow, e) : 0u, e);
+    // wave_shr:1, lane l takes lane l - 1 (lane 0: 0); dword 0 of a frame has nothing before it
+    const u32 below = __builtin_amdgcn_update_dpp(0u, v, 0x138, 0xF, 0xF, true);
+    const u32 prev = d ? below : 0u;
+    u32 u = v;                                                   // tap 0
+    for (u32 c = cpoly & ~1u; c; c &= c - 1u)                    // (uniform: the set taps 1 .. 31)
+        u ^= __builtin_amdgcn_alignbit(v, prev, 32u - (u32)__builtin_ctz(c));   // ({v, prev} >> (32 - j))
+    const u32 w = xf_lanes<D>(xf_dword(u), lane);
+    if (valid) {
+        if constexpr (D == 1) *(uint2 *)(out + frame * 2u) = make_uint2(w, 0u);
+        else out[frame * XROW + d] = w;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // 2048 < N <= 65536: one wave per frame, dword d = 64 r + lane in register r (R = D / 64).
 // N >= 131072 (MULTI): wave c of a frame's W = N / 65536 owns the 65536-bit chunk c; the
 // stages between chunks run on the loads (chunk c of the result is the XOR of every chunk c'
@@ -311,6 +342,31 @@ extern "C" int polar_sc_launch_xform_clear(uint64_t *p_dev, size_t n, void *stre
     if (blocks > 0x7FFFFFFFu) return -1;
     hipLaunchKernelGGL(polar_xf::polar_sc_xform_clear_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        (uint2 *)p_dev, n);
+    return (int)hipGetLastError();
+}
+
+// information rows -> codeword rows of the code precoded with conv_poly (bit j = c_j, c_0 = 1, judged
+// by the caller). 32 <= N <= 1024 a power of two, 1 <= K <= N, 1 <= batch <= 2^31 - 8. Returns as
+// polar_sc_launch_xform_clear.
+extern "C" int polar_sc_launch_encode_precoded(const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev, uint32_t N,
+                                               uint32_t K, size_t batch, uint32_t conv_poly, void *stream)
+{
+    int logD = 0;
+    while ((32u << logD) < N) logD++;
+    if (logD > 5) return (int)hipErrorInvalidValue;
+    const size_t blocks = ((batch << logD) + 64u * polar_xf::WAVES - 1u) / (64u * polar_xf::WAVES);
+    if (blocks > 0x7FFFFFFFu) return -1;
+    const dim3 g((unsigned)blocks), b(64 * polar_xf::WAVES);
+    switch (logD) {
+#define POLAR_XF_CASE(L)                                                                                       \
+    case L:                                                                                                    \
+        hipLaunchKernelGGL((polar_xf::polar_sc_encode_precoded_kernel<L>), g, b, 0, (hipStream_t)stream,       \
+                           (const polar_xf::Ent *)tab_dev, (const uint32_t *)in_dev, (uint32_t *)out_dev,      \
+                           (uint32_t)batch, 2u * ((K + 63u) / 64u), conv_poly);                                \
+        break;
+        POLAR_XF_CASE(0) POLAR_XF_CASE(1) POLAR_XF_CASE(2) POLAR_XF_CASE(3) POLAR_XF_CASE(4) POLAR_XF_CASE(5)
+#undef POLAR_XF_CASE
+    }
     return (int)hipGetLastError();
 }
 

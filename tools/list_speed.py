@@ -6,9 +6,11 @@ decoding rule, so the outputs are not compared). One warm-up of every way, then 
 interleaved rounds of --steps calls each; one JSON line per shape and way with the per-round
 times, their median and spread (max - min), frames per second, and for the list kernel its LDS
 per wave and waves per block. Written to --out as well when given
-(profiles/list_wide_speed.jsonl).
+(profiles/list_wide_speed.jsonl). --precode POLY,LEN adds decode_list(precode=(POLY, LEN)) of the same
+frames at every L to the same rounds (profiles/list_precoded_speed.jsonl).
 
-usage: python tools/list_speed.py [--steps 10] [--rounds 5] [--shapes name:frames,...] [--lists 1,2,...] [--out FILE]
+usage: python tools/list_speed.py [--steps 10] [--rounds 5] [--shapes name:frames,...] [--lists 1,2,...]
+                                  [--precode POLY,LEN] [--out FILE]
 """
 import argparse
 import json
@@ -31,7 +33,11 @@ def main():
     ap.add_argument("--shapes", default=SHAPES)
     ap.add_argument("--lists", default="1,2,4,8,16,32")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--precode", default=None, metavar="POLY,LEN",
+                    help="also time decode_list(precode=(POLY, LEN)) at every L, next to the plain call in the same "
+                         "rounds (DESIGN.md 3.11, Precoded codes; e.g. 0x6D,7)")
     args = ap.parse_args()
+    precode = tuple(int(x, 0) for x in args.precode.split(",")) if args.precode else None
     import torch
     import sc_polar_decoder_hls_amd as pkg
     from sc_polar_decoder_hls_amd import _plansets
@@ -52,6 +58,9 @@ def main():
         runs = {"decode_to_info": lambda: dec.decode_to_info(v, out=info)}
         for L in (int(x) for x in args.lists.split(",")):
             runs["decode_list L=%d" % L] = lambda L=L: dec.decode_list(v, L, crc=CRC, out=info, rank=rank)
+            if precode:     # (the same frames: the time of a walk does not depend on what the bits mean)
+                runs["decode_list precoded L=%d" % L] = lambda L=L: dec.decode_list(v, L, crc=CRC, out=info, rank=rank,
+                                                                                     precode=precode)
         for fn in runs.values():
             for _ in range(2):
                 fn()
@@ -68,6 +77,8 @@ def main():
             if k != "decode_to_info":
                 lds, wpb = pkg.list_shape(dec.N, int(k.split("=")[1]))
                 rec.update(lds_bytes_per_wave=lds, waves_per_block=wpb)
+                if "precoded" in k:
+                    rec.update(conv_poly=precode[0], conv_len=precode[1])
             lines.append(json.dumps(rec))
             print(lines[-1], flush=True)
         dec.close()
