@@ -448,6 +448,25 @@ int polar_sc_decode_list_precoded_to_info(const polar_sc_plan *plan, const int8_
 int polar_sc_encode_precoded(const polar_sc_plan *plan, const uint64_t *info_dev, uint64_t *x_dev, size_t batch,
                              uint32_t conv_poly, int conv_len, void *stream);
 
+/* ---- Soft-output decoding (SCAN), N <= 1024 ----
+ * Soft cancellation on the SC tree: the tree, visiting order and F of successive cancellation, with
+ * partial sums that are LLRs, passed up as extrinsic information and kept from one iteration to the
+ * next. llr_dev: int8 [batch][N] used by value, as in list decoding (only the plan's mask and N take
+ * part). ext_dev: int16 [batch][N], the extrinsic LLR of every codeword bit after `iterations` = 1 .. 8
+ * passes, in [-32766, 32766] or 32767 = "this bit is 0". hard_bits_dev (may be NULL): the rows of
+ * polar_sc_decode, bit i = [llr[i] + ext[i] < 0], ready for polar_sc_extract_info. K = 0 gives 32767
+ * everywhere, K = N gives 0 everywhere. One launch, one wave per frame, asynchronous on `stream`;
+ * nothing allocated after the first call or polar_sc_plan_prepare. batch == 0 returns 0; batch <=
+ * 2^31 - 8. -EINVAL: NULL plan, llr_dev or ext_dev, iterations outside 1 .. 8, llr_dev or ext_dev not
+ * 4-byte aligned, hard_bits_dev not 8-byte aligned; -ENOTSUP: N > 1024 or an LLR_BITS 9 plan. */
+int polar_sc_decode_scan(const polar_sc_plan *plan, const int8_t *llr_dev, size_t batch, int iterations,
+                         int16_t *ext_dev, uint64_t *hard_bits_dev, void *stream);
+
+/* Static LDS per wave (bytes) and waves per block of that kernel for N = 32 .. 1024 (a power of two)
+ * and iterations = 1 .. 8 (one iteration keeps no state between passes); zeros for anything else.
+ * Host only. */
+void polar_sc_scan_shape(uint32_t N, int iterations, uint32_t *lds_bytes_per_wave, uint32_t *waves_per_block);
+
 /* ---- Adaptive CRC-aided decoding, N <= 1024 ----
  * Successive cancellation first, the list decoder only for the frames whose SC result fails the
  * CRC, in one asynchronous call with no host round trip. The CRC is that of

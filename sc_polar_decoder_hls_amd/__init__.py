@@ -134,7 +134,7 @@ EXPORTS = (
     "polar_sc_decode_list_to_info", "polar_sc_decode_list_wide_to_info",
     "polar_sc_decode_list_precoded_to_info", "polar_sc_encode_precoded",
     "polar_sc_crc_check", "polar_sc_adaptive_workspace", "polar_sc_decode_adaptive_to_info",
-    "polar_sc_decode_adaptive_wide_to_info",
+    "polar_sc_decode_adaptive_wide_to_info", "polar_sc_decode_scan",
 )
 
 _lib = None
@@ -190,6 +190,8 @@ def lib():
         "polar_sc_decode_list_precoded_to_info": [p, p, sz, i32, u32, i32, u32, i32, p, p, p],
         "polar_sc_encode_precoded": [p, p, p, sz, u32, i32, p],
         "polar_sc_list_wide_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
+        "polar_sc_decode_scan": [p, p, sz, i32, p, p, p],
+        "polar_sc_scan_shape": [u32, i32, ctypes.POINTER(u32), ctypes.POINTER(u32)],
         "polar_sc_plan_get_stats": [p, p],
         "polar_sc_plan_get_schedule": [p, p, u32, ctypes.POINTER(u32)],
         "polar_sc_selftest_lanes": [p],
@@ -690,6 +692,32 @@ class Decoder:
                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(rank.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
         return out, rank
 
+    # -- soft-output decoding -------------------------------------------------------
+    def decode_scan(self, llr, iterations=1, out=None, hard=None, stream=None):
+        """Soft-output (SCAN) decoding of int8 LLRs [B, N] (N <= 1024), `iterations` = 1 .. 8 passes over
+        the SC tree: returns (ext, hard). ext: int16 [B, N], the extrinsic LLR of every codeword bit, in
+        [-32766, 32766] or 32767 for a bit known to be 0; llr + ext is the decoder's belief. hard: the
+        int64 rows [B, ceil(N/64)] of decode() (bit i = [llr[i] + ext[i] < 0], ready for extract_info), or
+        None with hard=False. `out` and `hard` may be tensors to fill. Asynchronous on `stream`."""
+        torch = self._check_llr(llr)
+        B = llr.shape[0]
+        if out is None:
+            out = torch.empty((B, self.N), dtype=torch.int16, device=llr.device)
+        else:
+            self._check_out(out, llr, (B, self.N), torch.int16)
+        if hard is None:
+            hard = torch.empty((B, self.words), dtype=torch.int64, device=llr.device)
+        elif hard is False:
+            hard = None
+        else:
+            self._check_out(hard, llr, (B, self.words), torch.int64)
+        with torch.cuda.device(llr.device):
+            s = stream if stream is not None else torch.cuda.current_stream(llr.device)
+            _check("polar_sc_decode_scan", lib().polar_sc_decode_scan(
+                self._plan, ctypes.c_void_p(llr.data_ptr()), B, int(iterations), ctypes.c_void_p(out.data_ptr()),
+                ctypes.c_void_p(hard.data_ptr() if hard is not None else None), ctypes.c_void_p(s.cuda_stream)))
+        return out, hard
+
     # -- adaptive CRC-aided decoding (DESIGN.md 3.12) -----------------------------------------------
     def crc_check(self, info, crc, out=None, stream=None):
         """Which rows of information words (torch.int64 CUDA [B, info_words], as decode_to_info and
@@ -853,6 +881,14 @@ def list_shape(N, list_size):
     lds, wpb = ctypes.c_uint32(0), ctypes.c_uint32(0)
     fn = lib().polar_sc_list_wide_shape if int(list_size) in (16, 32) else lib().polar_sc_list_shape
     fn(int(N), int(list_size), ctypes.byref(lds), ctypes.byref(wpb))
+    return lds.value, wpb.value
+
+
+def scan_shape(N, iterations):
+    """(LDS bytes per wave, waves per block) of decode_scan's kernel for (N, iterations); zeros when
+    there is none."""
+    lds, wpb = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().polar_sc_scan_shape(int(N), int(iterations), ctypes.byref(lds), ctypes.byref(wpb))
     return lds.value, wpb.value
 
 

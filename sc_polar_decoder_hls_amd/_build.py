@@ -15,7 +15,8 @@ SOURCES = [os.path.join(PKG, "csrc", "polar_sc_kernels.hip"), os.path.join(PKG, 
            os.path.join(PKG, "csrc", "polar_sc_jit.cpp"), os.path.join(PKG, "csrc", "polar_sc_pairgen.cpp"),
            os.path.join(PKG, "csrc", "polar_sc_channel.hip"), os.path.join(PKG, "csrc", "polar_sc_xform.hip"),
            os.path.join(PKG, "csrc", "polar_sc_soft.hip"), os.path.join(PKG, "csrc", "polar_sc_tables.cpp"),
-           os.path.join(PKG, "csrc", "polar_sc_list.hip"), os.path.join(PKG, "csrc", "polar_sc_adaptive.hip")]
+           os.path.join(PKG, "csrc", "polar_sc_list.hip"), os.path.join(PKG, "csrc", "polar_sc_adaptive.hip"),
+           os.path.join(PKG, "csrc", "polar_sc_scan.hip")]
 SOFT_SRC = os.path.join(PKG, "csrc", "polar_sc_soft.hip")
 DEVICE_H = os.path.join(PKG, "csrc", "polar_sc_device.h")
 INTERP_H = os.path.join(PKG, "csrc", "polar_sc_interp.h")

@@ -43,6 +43,9 @@ extern "C" int polar_sc_launch_list_precoded(const void *tab_dev, const int8_t *
                                              uint64_t *info_dev, uint8_t *rank_dev, void *stream);
 extern "C" int polar_sc_launch_encode_precoded(const void *tab_dev, const uint64_t *in_dev, uint64_t *out_dev, uint32_t N,
                                                uint32_t K, size_t batch, uint32_t conv_poly, void *stream);
+// polar_sc_scan.hip: soft-output (SCAN) decoding of N <= 1024 (reads the same mask table)
+extern "C" int polar_sc_launch_scan(const void *tab_dev, const int8_t *llr_dev, size_t batch, uint32_t N, int iterations,
+                                    int16_t *ext_dev, uint64_t *hard_dev, void *stream);
 extern "C" size_t polar_sc_crc_table_dwords(uint32_t K, uint32_t c);
 extern "C" void polar_sc_crc_table(uint32_t K, uint32_t poly, uint32_t c, uint32_t *tab);
 extern "C" int polar_sc_launch_crc_check(const void *tab_dev, const uint64_t *info_dev, size_t batch, uint32_t K,
@@ -1488,6 +1491,21 @@ int polar_sc_encode_precoded(const polar_sc_plan *p, const uint64_t *info_dev, u
     const int rc = polar_sc_launch_encode_precoded(tab, info_dev, x_dev, p->N, p->K, batch, conv_poly, stream);
     if (rc < 0) return -EINVAL;
     return rc ? hip_fail("precoded encode launch", (hipError_t)rc) : 0;
+}
+
+// ---- soft-output decoding (include/polar_sc.h) ------------------------------------
+int polar_sc_decode_scan(const polar_sc_plan *p, const int8_t *llr_dev, size_t batch, int iterations, int16_t *ext_dev,
+                         uint64_t *hard_bits_dev, void *stream)
+{
+    if (!p || iterations < 1 || iterations > 8) return -EINVAL;
+    if (p->N > 1024u || p->cfg.llr_bits > 8) return -ENOTSUP;
+    if (batch == 0) return 0;
+    if (!llr_dev || !ext_dev || ((uintptr_t)llr_dev & 3u) || ((uintptr_t)ext_dev & 3u)) return -EINVAL;
+    if (((uintptr_t)hard_bits_dev & 7u) || batch > (size_t)0x7FFFFFF8) return -EINVAL;
+    const void *tab = nullptr;
+    if (const int e = ensure_xform(p, &tab)) return e;
+    const int rc = polar_sc_launch_scan(tab, llr_dev, batch, p->N, iterations, ext_dev, hard_bits_dev, stream);
+    return rc ? hip_fail("scan decode launch", (hipError_t)rc) : 0;
 }
 
 // ---- adaptive CRC-aided decoding (include/polar_sc.h) -----------------------------
